@@ -5,10 +5,14 @@ loss + backward + gradient all-reduce + Adam) on synthetic 384x384 batches.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One process per GPU (RCCL over xGMI for N > 1), weak scaling (fixed per-GPU batch).
-Prints ONE JSON line on rank 0 (contract in the task statement), including
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the --steps steps and prints the headline (`value`,
+`ms_per_step`, ...).  Everything else this file measures runs only with `--full`:
   roofline     -- the dominant kernel (the implicit-GEMM 3x3 conv 512->512 of the heads),
                   timed live with HIP events on its launch stream;
-  cpu_baseline -- the CPU oracle on the host cores (rank 0, N == 1 only).
+  cpu_baseline -- the CPU oracle on the host cores (rank 0, N == 1 only);
+  alt_*        -- the non-headline forms of the same workload (other sdf-head forms, precisions);
+  the host's enqueue time into a drained queue, and (N > 1) the traced gradient exchange of one more step.
+`--dump-outputs DIR` writes what the timed path returned in its last timed step as DIR/<name>.npy (rank 0).
 
 Workloads (BASELINE.json configs): cfg2 (default; configs[1], the one the metric is quoted on; configs[2] is the same at
 N = 8), cfg1 (configs[0]: ViT-S/16 224x224 batch 2 forward only), cfg4 (configs[3]: ViT-L/14 518x518 batch 16 train step),
@@ -60,6 +64,8 @@ SWEEP_CHECK = (600, 620)   # cfg5: the proposals the CPU oracle is TIMED on (20 
 SWEEP_CHECK_IDX = sorted(set(range(0, 900, 6)) | set(range(900, 1140, 3)) | set(range(1140, 1225)))
 PEAK_BF16_TFLOPS = 2500.0  # dense bf16 MFMA, MI355X_MICROARCH.md
 PEAK_F32_TFLOPS = 157.3
+DUMP_BYTES = 64 * 10 ** 6  # --dump-outputs: at most this many bytes of .npy files in all, headers included
+NPY_HEADER_BYTES = 4096    # per file: an upper bound of an .npy header (128 bytes for the shapes written here)
 
 
 def forward_gflop_per_image(cfg, H, W):
@@ -96,6 +102,25 @@ def anchors(height, width):
     out[:, 2][out[:, 2] >= width] = width
     out[:, 3][out[:, 3] >= height] = height
     return np.concatenate((out, [[0, 0, width, height]]), 0)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: one out_dir/<name>.npy per array, float64 where the path returns float64 or integers (exact), float32
+    otherwise.  An array whose file would exceed its equal share of DUMP_BYTES is written as a fixed, seeded sample of its
+    flattened elements: the same positions in every run with the same arguments, so two builds compare element for element."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    share = DUMP_BYTES // max(len(arrays), 1) - NPY_HEADER_BYTES     # data bytes per file
+    for name, t in arrays.items():
+        wide = t.dtype in (torch.float64, torch.int64, torch.int32)
+        t = t.detach()
+        item = 8 if wide else 4
+        if t.numel() * item > share:
+            rng = np.random.default_rng(1234)
+            pos = np.unique(rng.integers(0, t.numel(), share // item))
+            t = t.reshape(-1)[torch.from_numpy(pos).to(t.device)]
+        np.save(os.path.join(out_dir, name + ".npy"), t.to("cpu", torch.float64 if wide else torch.float32).numpy())
 
 
 # ----------------------------------------------------------------------------------------------- CPU baseline
@@ -473,10 +498,11 @@ def run_rank(a):
         for p in net.parameters():
             p.requires_grad = False
         img = torch.from_numpy(synth.make_batch(B, H, W, seed=rank)[0]).to(dev)
+        last = [None]
 
         def one():
             with torch.no_grad():
-                net.get_prediction(img)
+                last[0] = net.get_prediction(img)
         units_per_step = B
     else:  # sweep: one step = one 640x480 image = 1225 proposals (replicas only: every rank sweeps its own images)
         # hash weights + the peak fixtures' documented edits: a plain random-init net has empty eroded masks everywhere and the
@@ -493,14 +519,14 @@ def run_rank(a):
         n_img = max(1, min(4, a.steps))
         images = [torch.from_numpy(synth.blob_images(1, Hi, Wi, seed=1000 * rank + i)[0]).to(dev) for i in range(n_img)]
         counter = [0]
-        peaks = [0, 0]
+        peaks = [0, 0, None]
         M_head = 50 * 128 * 128
 
         def one():
             image = images[counter[0] % n_img]
             counter[0] += 1
             inf = {}
-            peaks[0], peaks[1], _ = reasoning.sweep_proposals(net, image, props, 50, n_streams=a.sweep_streams, precision=a.sweep_precision, info=inf)
+            peaks[0], peaks[1], peaks[2] = reasoning.sweep_proposals(net, image, props, 50, n_streams=a.sweep_streams, precision=a.sweep_precision, info=inf)
             sweep_stats[0] += inf.get("proposals", 0)
             sweep_stats[1] += inf.get("rerun", 0) or 0
         sweep_stats = [0, 0]
@@ -525,7 +551,7 @@ def run_rank(a):
     for _ in range(warm):
         one()
     barrier()
-    if not graphed:
+    if a.full and not graphed:
         ops.set_kernel_timer(is_head_conv)
     host_s = 0.0
     t0 = time.perf_counter()
@@ -535,37 +561,51 @@ def run_rank(a):
         host_s += time.perf_counter() - th
     barrier()
     elapsed = time.perf_counter() - t0
-    if graphed:
-        # separate eager leg for the roofline's kernel timing (events on the launch stream around every head-conv launch)
-        ops.set_kernel_timer(is_head_conv)
-        for _ in range(2):
+    if a.dump_outputs and rank == 0:
+        # what a caller of the timed path holds after its last timed step, written before any --full leg runs the path again
+        if kind == "train":
+            named = [n for n, _ in net.named_parameters() if n in step.G]
+            P = dict(net.named_parameters())
+            outs = {"loss_terms": last[0],     # [total, center, sdf, grad, bce]
+                    "params": torch.cat([P[n].detach().reshape(-1) for n in named]),     # the updated weights, named_parameters order
+                    "grads": torch.cat([step.G[n].reshape(-1) for n in named])}        # the step's gradients, same order
+        elif kind == "forward":
+            outs = dict(last[0])
+        else:
+            outs = {"max_values": peaks[0], "flat_argmax": peaks[1], "deltas": peaks[2]}
+        dump_outputs(a.dump_outputs, outs)
+        del outs
+    conv_modes, conv_ms, drained, ar_trace = [], [], [], None
+    if a.full:
+        if graphed:
+            # separate eager leg for the roofline's kernel timing (events on the launch stream around every head-conv launch)
+            ops.set_kernel_timer(is_head_conv)
+            for _ in range(2):
+                one()
+        conv_modes = ops.kernel_timer_results_ms(with_modes=True)
+        conv_ms = [m for m, _ in conv_modes]
+        ops.set_kernel_timer(None)
+        # the host's OWN work per step: the time to enqueue one step into an EMPTY queue.  host_s above is measured with steps queued back to
+        # back: once the stream's queue is full of 30-ms kernels the launch call blocks, and that waiting is counted too (cfg2: ~190 of a
+        # 226-ms step, against ~6 ms of work -- tools/enqueue_time.py)
+        for _ in range(3):
+            torch.cuda.synchronize()
+            th = time.perf_counter()
             one()
-    conv_modes = ops.kernel_timer_results_ms(with_modes=True)
-    conv_ms = [m for m, _ in conv_modes]
-    ops.set_kernel_timer(None)
-    # the host's OWN work per step: the time to enqueue one step into an EMPTY queue.  host_s above is measured with steps queued back to
-    # back: once the stream's queue is full of 30-ms kernels the launch call blocks, and that waiting is counted too (cfg2: ~190 of a
-    # 226-ms step, against ~6 ms of work -- tools/enqueue_time.py)
-    drained = []
-    for _ in range(3):
+            drained.append(time.perf_counter() - th)
         torch.cuda.synchronize()
-        th = time.perf_counter()
-        one()
-        drained.append(time.perf_counter() - th)
-    torch.cuda.synchronize()
-    ar_trace = None
-    if dist_on and kind == "train":
-        # one more, untimed step with the exchange traced: per bucket, when its all-reduce was issued and when it completed, against
-        # the end of backward (parallel.BucketedAllReduce.trace_report) -- how much of the exchange hides behind backward
-        # (never at the price of the line: whatever goes wrong here is reported in place of the trace)
-        try:
-            step.comm.trace = True
-            one()
-            ar_trace = step.comm.trace_report()
-        except Exception as e:   # noqa: BLE001
-            ar_trace = {"error": f"{type(e).__name__}: {e}"}
-        step.comm.trace = False
-        barrier()
+        if dist_on and kind == "train":
+            # one more, untimed step with the exchange traced: per bucket, when its all-reduce was issued and when it completed, against
+            # the end of backward (parallel.BucketedAllReduce.trace_report) -- how much of the exchange hides behind backward
+            # (never at the price of the line: whatever goes wrong here is reported in place of the trace)
+            try:
+                step.comm.trace = True
+                one()
+                ar_trace = step.comm.trace_report()
+            except Exception as e:   # noqa: BLE001
+                ar_trace = {"error": f"{type(e).__name__}: {e}"}
+            step.comm.trace = False
+            barrier()
     own = gather_over_ranks(elapsed)
     elapsed = max_over_ranks(elapsed)
 
@@ -616,25 +656,27 @@ def run_rank(a):
             "peak_hbm_gib": round(torch.cuda.max_memory_allocated() / 2 ** 30, 1),
             # host time spent enqueueing one step (no synchronisation inside): what a HIP-graph replay removes
             "host_enqueue_ms_per_step": 1e3 * host_s / a.steps,
-            "host_enqueue_ms_per_step_queue_drained": 1e3 * sorted(drained)[1],
-            "host_enqueue_note": "the first figure is taken with steps queued back to back and includes the launch calls' blocking on a full queue; "
-                                 "the second is one step enqueued into an empty queue (median of 3, untimed leg): the host's own work",
             "hip_graph": ({"mode": a.graphs, "replayed": True, "warmup_calls_untimed": warm,
                            "form": ("chain of per-stage graphs on two streams (graphs.StagedCaptured)" if kind == "train" and graphs.STAGED and WgradStream.wanted(pixels)
-                                    else "one graph"),
-                           "roofline_timing": "separate eager leg of 2 steps after the timed region (no per-kernel events inside a replay)"}
+                                    else "one graph")}
                           if graphed else {"mode": a.graphs, "replayed": False}),
-            "roofline": {"bound": "mfma",
-                         "kernel": ("umr_gemm_nt implicit-GEMM conv3x3 512->512 of the heads ("
-                                    + ("per step: the centre head's forward launch + its ReLU-masked data gradient (+ the boundary-distance head's forward launch "
-                                       "in 'factored' mode); the boundary-distance head is algebraic and the weight gradient is the TN kernel" if kind == "train" else "forward: the centre head's launch of every batch; the boundary-distance head runs collapsed")
-                                    + (") bf16" if a.dtype == "bf16" else (") fp32-grade: f32 values as three bf16 planes, six bf16 MFMA products per "
-                                                                          "f32 product; peak = 2500 / 6" if x3 else ") f32 MFMA"))),
-                         "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
-                         "launches_timed": len(conv_ms), "avg_launch_ms": avg_ms, "flop_per_launch": conv_flop,
-                         **measured_traffic(a, M_head)},
         }
-        if six_term is not None:
+        if a.full:
+            res["host_enqueue_ms_per_step_queue_drained"] = 1e3 * sorted(drained)[1]
+            res["host_enqueue_note"] = ("the first figure is taken with steps queued back to back and includes the launch calls' blocking on a full "
+                                        "queue; the second is one step enqueued into an empty queue (median of 3, untimed leg): the host's own work")
+            if graphed:
+                res["hip_graph"]["roofline_timing"] = "separate eager leg of 2 steps after the timed region (no per-kernel events inside a replay)"
+            res["roofline"] = {"bound": "mfma",
+                               "kernel": ("umr_gemm_nt implicit-GEMM conv3x3 512->512 of the heads ("
+                                          + ("per step: the centre head's forward launch + its ReLU-masked data gradient (+ the boundary-distance head's forward launch "
+                                             "in 'factored' mode); the boundary-distance head is algebraic and the weight gradient is the TN kernel" if kind == "train" else "forward: the centre head's launch of every batch; the boundary-distance head runs collapsed")
+                                          + (") bf16" if a.dtype == "bf16" else (") fp32-grade: f32 values as three bf16 planes, six bf16 MFMA products per "
+                                                                                "f32 product; peak = 2500 / 6" if x3 else ") f32 MFMA"))),
+                               "achieved": achieved, "peak": peak, "unit": "TFLOP/s", "frac": achieved / peak,
+                               "launches_timed": len(conv_ms), "avg_launch_ms": avg_ms, "flop_per_launch": conv_flop,
+                               **measured_traffic(a, M_head)}
+        if six_term is not None and a.full:
             res["roofline"]["six_term_launches"] = six_term
             res["roofline"]["kernel"] = res["roofline"]["kernel"].replace("six bf16 MFMA products per f32 product; peak = 2500 / 6",
                                                                           "pass 1 of the certificate-driven sweep: THREE bf16 MFMA products per f32 product; peak = 2500 / 3")
@@ -678,7 +720,7 @@ def run_rank(a):
                                   "source_image": list(wl["image"]),
                                   "stages": "crop+resize, ObjectnessNet maps, centre peak picking, boundary box deltas"})
             res["est_minutes_for_5000_images"] = 5000.0 / res["value"] / 60.0
-            if a.sweep_streams > 1:
+            if a.full and a.sweep_streams > 1:
                 res["roofline"]["note"] = ("batches on different HIP streams share the chip: a conv launch is timed while kernels of the other "
                                            "streams run beside it, so `achieved` is a lower bound of the kernel alone (--sweep-streams 1)")
             res["maps_with_peak"] = int((peaks[0] > 0).sum().item())
@@ -694,7 +736,7 @@ def run_rank(a):
         hip_peaks = None
         if kind == "sweep":
             res["maps_with_peak_share"] = res["maps_with_peak"] / wl["proposals"]
-        if not dist_on and kind == "sweep" and not a.no_alt:
+        if a.full and not dist_on and kind == "sweep" and not a.no_alt:
             def timed_sweeps(n):
                 one()
                 torch.cuda.synchronize()
@@ -779,7 +821,7 @@ def run_rank(a):
         if kind != "train":
             res["sdf_head"] = ("inference default 'auto': the boundary-distance head (no non-linearity before its tanh, objectness_net.py:128-135) "
                                "evaluated as one 3x3 conv 256 -> 1 on the map before the final resize; 'factored' leg beside it")
-        if not dist_on and kind == "forward" and not a.no_alt:
+        if a.full and not dist_on and kind == "forward" and not a.no_alt:
             # the same call with the boundary-distance head as the reference's four convolutions (A/B of the inference default)
             net.set_sdf_head_mode("factored")
             for _ in range(graphs.WARMUP_CALLS + 2):
@@ -793,7 +835,7 @@ def run_rank(a):
             net.set_sdf_head_mode("auto")
             res["alt_factored_sdf_head"] = {"value": B / dtf, "unit": "images/sec", "ms_per_step": 1e3 * dtf,
                                             "note": "set_sdf_head_mode('factored'): the head's four convolutions as the reference runs them"}
-        if not dist_on and kind == "train" and a.workload == "cfg2" and not a.no_alt:
+        if a.full and not dist_on and kind == "train" and a.workload == "cfg2" and not a.no_alt:
             # outside the timed region, reported BESIDE the headline: the same step with the boundary-distance head in its other forms
             # (identical function and gradients up to rounding, tests/test_train_gpu.py::
             # test_collapsed_sdf_head_equals_factored, tests/test_collapsed_train_gpu.py)
@@ -819,7 +861,7 @@ def run_rank(a):
             res["alt_gemm_backward_sdf_head"] = alt_leg("factored forward + boundary-distance head backward as layer-by-layer GEMMs (the reference's own schedule of operations)")
             net.set_linear_head_backward("algebraic")
             net.set_sdf_head_mode("auto")
-        if not dist_on and not a.no_cpu_baseline:
+        if a.full and not dist_on and not a.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline(wl, hip_peaks)
         print(json.dumps(res), flush=True)
     if dist_on:
@@ -899,8 +941,14 @@ def main():
                          "unmore_amd/parallel.py, DESIGN.md section 6)")
     ap.add_argument("--cu-budget", type=int, default=0,
                     help="CUs the persistent GEMM grids occupy (umr_set_cu_budget; 0 = all): leaves the rest to RCCL's kernels when world > 1")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-alt", action="store_true", help="skip the extra (non-headline) factored-sdf-head / GEMM-backward measurements")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the roofline kernel timing, the drained-queue enqueue time, the traced gradient exchange "
+                         "(N > 1), the non-headline alt_* legs and the CPU baseline; a plain run times the headline steps only")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-alt", action="store_true", help="--full without the extra (non-headline) factored-sdf-head / GEMM-backward measurements")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy (float32 / float64, "
+                         "rank 0, at most 64 MB in all: larger arrays as a fixed seeded sample)")
     a = ap.parse_args()
     if a.dtype is None:
         a.dtype = "fp32" if WORKLOADS[a.workload]["kind"] == "sweep" else "bf16"

@@ -110,3 +110,34 @@ def test_a_dying_rank_five_of_eight_ends_the_launch_within_seconds():
     assert r.returncode == 3, (r.returncode, r.stderr[-2000:])
     assert time.time() - t0 < 30
     assert "rank 5 exited with status 3" in r.stderr and not [l for l in r.stdout.splitlines() if l.startswith("{")]
+
+
+def test_dump_outputs_stays_within_its_budget_and_samples_the_same_positions(tmp_path):
+    """bench.dump_outputs on host tensors: float32 / float64 files (integers exactly, as float64), an array above its share of the
+    64-MB budget written as a seeded sample -- the same positions in every call, so two builds' dumps compare element for element"""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    big = torch.arange(12 * 2 ** 20, dtype=torch.float64)      # 96 MB
+    small = torch.linspace(-1, 1, 1000, dtype=torch.bfloat16)
+    idx = torch.arange(7, dtype=torch.int64) * 3_000_000_000
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small, "idx": idx})
+    total = sum(os.path.getsize(tmp_path / "a" / f) for f in os.listdir(tmp_path / "a"))
+    assert sorted(os.listdir(tmp_path / "a")) == ["big.npy", "idx.npy", "small.npy"] and total <= bench.DUMP_BYTES
+    a = {k: np.load(tmp_path / "a" / f"{k}.npy") for k in ("big", "small", "idx")}
+    b = {k: np.load(tmp_path / "b" / f"{k}.npy") for k in ("big", "small", "idx")}
+    assert a["big"].dtype == np.float64 and a["small"].dtype == np.float32 and a["idx"].dtype == np.float64
+    assert np.array_equal(a["idx"], idx.numpy().astype(np.float64)) and np.array_equal(a["small"], small.float().numpy())
+    # the sample: distinct sorted positions (the values of arange are their positions), identical in both calls
+    assert 0 < a["big"].size < big.numel() and np.all(np.diff(a["big"]) > 0) and np.array_equal(a["big"], b["big"])
+
+
+def test_dump_outputs_counts_the_npy_header_in_its_budget(tmp_path):
+    """an array whose data alone is exactly the budget is sampled: the file, header included, stays within DUMP_BYTES"""
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    bench.dump_outputs(str(tmp_path), {"x": torch.zeros(bench.DUMP_BYTES // 4, dtype=torch.float32)})
+    assert os.path.getsize(tmp_path / "x.npy") <= bench.DUMP_BYTES

@@ -6,6 +6,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -32,7 +33,7 @@ def test_two_ranks_spawned_by_bench_itself():
 def test_two_ranks_with_the_bf16_gradient_wire():
     """`--dp-wire bf16` end to end (2 gloo ranks on the one GPU, miniature workload): the line says which wire was used, the step runs and
     trains (finite loss); the exchange's accuracy is tests/test_parallel_cpu.py's and tests/test_dp_gpu.py's business"""
-    res = _run("--gpus", "2", "--workload", "tiny", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--dp-wire", "bf16")
+    res = _run("--gpus", "2", "--workload", "tiny", "--backend", "gloo", "--steps", "3", "--warmup", "1", "--dp-wire", "bf16", "--full")
     assert res["n_gpus"] == 2 and res["collective"]["gradient_wire"] == "bf16" and res["value"] > 0
     assert res["final_loss"] == res["final_loss"] and 0 < res["final_loss"] < 100
     tr = res.get("allreduce_trace_rank0")
@@ -42,7 +43,7 @@ def test_two_ranks_with_the_bf16_gradient_wire():
 @pytest.mark.parametrize("workload,extra", [("tiny", []), ("cfg1", []), ("cfg5", ["--steps", "1", "--warmup", "1"]),
                                             ("cfg4", ["--steps", "1", "--warmup", "1", "--no-alt"])])
 def test_single_gpu_lines_carry_the_contract(workload, extra):
-    res = _run("--workload", workload, "--no-cpu-baseline", *(extra or ["--steps", "2", "--warmup", "1"]))
+    res = _run("--workload", workload, "--full", "--no-cpu-baseline", *(extra or ["--steps", "2", "--warmup", "1"]))
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline"):
         assert k in res, k
@@ -63,3 +64,47 @@ def test_single_gpu_lines_carry_the_contract(workload, extra):
         sp, full = res["sweep_precision"], res["alt_fp32_full_precision"]
         assert sp["mode"] == "certified" and 0.0 <= sp["rerun_fraction"] < 0.5, sp
         assert full["peak_index_differs_from_headline"] == 0 and full["max_abs_amax_difference_vs_headline"] <= 1.5e-4, full
+
+
+@pytest.mark.parametrize("workload", ["tiny", "cfg1", "cfg5"])
+def test_plain_run_times_the_headline_only_and_dumps_its_outputs(workload, tmp_path):
+    """without --full the line carries the headline and nothing measured outside the timed steps; --dump-outputs writes what the
+    timed path returned in its last step, float32 / float64, and a second run with the same arguments starts from the same inputs"""
+    runs = []
+    for i in range(2):
+        d = tmp_path / f"run{i}"
+        steps = 1 if workload == "cfg5" else 3
+        res = _run("--workload", workload, "--steps", str(steps), "--warmup", "1", "--dump-outputs", str(d))
+        assert res["steps"] == steps and res["warmup"] == 1 and res["ms_per_step"] > 0 and res["value"] > 0
+        per_step = 1 if workload == "cfg5" else res["config"]["per_gpu_batch"]      # cfg5: one step = one image
+        assert abs(res["value"] - per_step * 1e3 / res["ms_per_step"]) <= 1e-6 * res["value"]
+        for k in ("roofline", "cpu_baseline", "host_enqueue_ms_per_step_queue_drained"):
+            assert k not in res, k
+        assert not [k for k in res if k.startswith("alt_")]
+        files = sorted(os.listdir(d))
+        assert files == {"tiny": ["grads.npy", "loss_terms.npy", "params.npy"], "cfg1": ["center_fields.npy", "sdf_maps.npy"],
+                         "cfg5": ["deltas.npy", "flat_argmax.npy", "max_values.npy"]}[workload]
+        arrs = {f[:-4]: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrs.values())
+        assert sum((d / f).stat().st_size for f in files) <= 64 * 10 ** 6
+        runs.append(arrs)
+    if workload == "tiny":
+        assert runs[0]["loss_terms"].shape == (5,)
+        np.testing.assert_allclose(runs[0]["loss_terms"], runs[1]["loss_terms"], rtol=1e-4, atol=1e-6)
+        np.testing.assert_allclose(runs[0]["params"], runs[1]["params"], rtol=0, atol=1e-3)
+    elif workload == "cfg5":
+        # the sweep of one 640x480 image: per proposal the peak score, its flat index in the 128x128 crop (integers, written as float64)
+        # and the box deltas; the scores are not empty (the line's maps_with_peak), and a second run gives the same peaks
+        r = runs[1]      # the second run, whose line is `res`
+        assert r["max_values"].shape == (1225,) and r["flat_argmax"].shape == (1225,) and r["deltas"].shape == (1225, 4)
+        assert r["max_values"].dtype == np.float64 and r["flat_argmax"].dtype == np.float64 and r["deltas"].dtype == np.float32
+        am = r["flat_argmax"]
+        assert np.array_equal(am, np.round(am)) and am.min() >= 0 and am.max() < 128 * 128
+        assert int((r["max_values"] > 0).sum()) == res["maps_with_peak"] >= 1225 // 2
+        assert np.array_equal(runs[0]["flat_argmax"], runs[1]["flat_argmax"])
+        np.testing.assert_allclose(runs[0]["max_values"], runs[1]["max_values"], rtol=0, atol=1e-4)
+        np.testing.assert_allclose(runs[0]["deltas"], runs[1]["deltas"], rtol=0, atol=1e-3)
+    else:
+        assert runs[0]["sdf_maps"].shape[0] == 2 and runs[0]["sdf_maps"].shape[-2:] == (224, 224)
+        for k in runs[0]:
+            np.testing.assert_allclose(runs[0][k], runs[1][k], rtol=0, atol=1e-2)

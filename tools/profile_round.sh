@@ -11,7 +11,7 @@ OUT=$ROOT/gpurun_out/prof_${TAG}_${WL}
 rm -rf $OUT
 mkdir -p $OUT $ROOT/profiles
 export TMPDIR=/tmp
-ARGS="--workload $WL --steps 3 --warmup 2 --no-cpu-baseline --no-alt"
+ARGS="--full --workload $WL --steps 3 --warmup 2 --no-cpu-baseline --no-alt"
 cd /tmp
 rocprofv3 --kernel-trace --stats -d $OUT/stats -o run --output-format csv -- python3 $ROOT/bench.py $ARGS > $OUT/stats.log 2>&1
 echo "stats pass done"

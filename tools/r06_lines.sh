@@ -4,13 +4,13 @@
 mkdir -p gpurun_out/profiles_out
 OUT=gpurun_out/profiles_out/r06_bench_lines.jsonl
 : > $OUT
-python bench.py --steps 20 --warmup 5 2> gpurun_out/r6_line_cfg2.err | grep '"metric"' >> $OUT; echo "cfg2 done"
-python bench.py --workload cfg4 --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | grep '"metric"' >> $OUT; echo "cfg4 done"
-python bench.py --workload cfg1 --steps 50 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '"metric"' >> $OUT; echo "cfg1 done"
-python bench.py --workload ref --steps 50 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '"metric"' >> $OUT; echo "ref done"
-python bench.py --workload ref --graphs off --steps 50 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '"metric"' >> $OUT; echo "ref eager done"
-python bench.py --workload ref --dtype fp32 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '"metric"' >> $OUT; echo "ref fp32 done"
-python bench.py --workload cfg5 --steps 3 --warmup 1 2> gpurun_out/r6_line_cfg5.err | grep '"metric"' >> $OUT; echo "cfg5 done"
+python bench.py --full --steps 20 --warmup 5 2> ${OUT%.jsonl}_cfg2.err | grep '"metric"' >> $OUT; echo "cfg2 done"
+python bench.py --full --workload cfg4 --steps 10 --warmup 3 --no-cpu-baseline 2>/dev/null | grep '"metric"' >> $OUT; echo "cfg4 done"
+python bench.py --full --workload cfg1 --steps 50 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '"metric"' >> $OUT; echo "cfg1 done"
+python bench.py --full --workload ref --steps 50 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '"metric"' >> $OUT; echo "ref done"
+python bench.py --full --workload ref --graphs off --steps 50 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '"metric"' >> $OUT; echo "ref eager done"
+python bench.py --full --workload ref --dtype fp32 --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | grep '"metric"' >> $OUT; echo "ref fp32 done"
+python bench.py --full --workload cfg5 --steps 3 --warmup 1 2> ${OUT%.jsonl}_cfg5.err | grep '"metric"' >> $OUT; echo "cfg5 done"
 AB=gpurun_out/profiles_out/r06_adam_pack_ab.txt
 echo "# reference recipe (dpt_large, 128x128, batch 20, bf16, chain of per-stage graphs), same box, alternating: UMR_ADAM_PACK=0 (Adam launch + batched refresh of the" > $AB
 echo "# packed copies per stage, round 5) against 1 (one optimizer launch per stage that writes the Linear weights' bf16 copies itself, round 6)" >> $AB

@@ -6,9 +6,9 @@ OUT=gpurun_out/profiles_out/r06_rccl_one_rank.jsonl
 : > $OUT
 for wl in cfg2 ref; do
   if [ $wl = cfg2 ]; then S="--steps 10 --warmup 3"; else S="--steps 50 --warmup 5"; fi
-  python bench.py --workload $wl $S --no-cpu-baseline --no-alt 2> gpurun_out/rccl1_${wl}_plain.err | grep '"metric"' >> $OUT; echo "$wl plain done"
-  UMR_DP_FORCE=1 python bench.py --workload $wl $S --no-cpu-baseline --no-alt 2> gpurun_out/rccl1_${wl}_f32.err | grep '"metric"' >> $OUT; echo "$wl rccl f32 done"
-  UMR_DP_FORCE=1 python bench.py --workload $wl $S --dp-wire bf16 --no-cpu-baseline --no-alt 2> gpurun_out/rccl1_${wl}_bf16.err | grep '"metric"' >> $OUT; echo "$wl rccl bf16 done"
+  python bench.py --full --workload $wl $S --no-cpu-baseline --no-alt 2> ${OUT%.jsonl}_${wl}_plain.err | grep '"metric"' >> $OUT; echo "$wl plain done"
+  UMR_DP_FORCE=1 python bench.py --full --workload $wl $S --no-cpu-baseline --no-alt 2> ${OUT%.jsonl}_${wl}_f32.err | grep '"metric"' >> $OUT; echo "$wl rccl f32 done"
+  UMR_DP_FORCE=1 python bench.py --full --workload $wl $S --dp-wire bf16 --no-cpu-baseline --no-alt 2> ${OUT%.jsonl}_${wl}_bf16.err | grep '"metric"' >> $OUT; echo "$wl rccl bf16 done"
 done
 python - <<'P'
 import json

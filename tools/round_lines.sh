@@ -6,13 +6,13 @@ mkdir -p gpurun_out/profiles_out
 OUT=gpurun_out/profiles_out/${TAG}_bench_lines.jsonl
 : > $OUT
 run() { echo "== $*" >&2; python bench.py "$@" 2>gpurun_out/round_lines.err | grep '^{' >> $OUT; }
-run                                             # cfg2: the driver's default line (with cpu_baseline and the alt legs)
-run --workload cfg1
-run --workload cfg4 --steps 5
-run --workload ref --steps 10
-run --workload ref --dtype fp32 --steps 10
-run --workload ref --steps 10 --graphs off --no-cpu-baseline   # the eager two-stream schedule (A/B of the default: chain of per-stage graphs)
-run --workload cfg5 --steps 2 --warmup 1
+run --full                                      # cfg2: the default workload's line with cpu_baseline and the alt legs
+run --full --workload cfg1
+run --full --workload cfg4 --steps 5
+run --full --workload ref --steps 10
+run --full --workload ref --dtype fp32 --steps 10
+run --full --workload ref --steps 10 --graphs off --no-cpu-baseline   # the eager two-stream schedule (A/B of the default: chain of per-stage graphs)
+run --full --workload cfg5 --steps 2 --warmup 1
 python - <<PY
 import json
 for l in open("$OUT"):
