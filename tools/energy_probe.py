@@ -3,8 +3,7 @@ resource the head conv runs out of -- MI355X_MICROARCH.md 'DVFS give-back', cdna
 
 Runs ONE kernel back to back on random operands for --seconds while a thread samples the board power from the amdgpu hwmon
 (power1_average, uW; fallback: rocm-smi --showpower), and reports ms / launch, TFLOP/s, average W, J / launch and pJ / FLOP.
-Variants of the library are separate builds selected with UMR_LIB (tools/probe/build_exp_lib.sh) or run-time switches given
-as environment variables, one process per variant on the SAME box (tools/probe/energy_ab.sh):
+Variants of the library are separate builds selected with UMR_LIB, one process per variant on the SAME box:
 
     python tools/energy_probe.py --kernel conv_nt|conv_nt_masked|conv_tn|g1x1_nt|conv_x3 [--seconds 6] [--tag name]"""
 import argparse

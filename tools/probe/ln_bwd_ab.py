@@ -1,4 +1,4 @@
-"""LayerNorm backward at the cfg2 token count (36928 x 768 bf16): python tools/probe/ln_bwd_ab.py  (UMR_LIB / UMR_LN_BWD_WG_PER_CU vary)"""
+"""LayerNorm backward at the cfg2 token count (36928 x 768 bf16): python tools/probe/ln_bwd_ab.py  (UMR_LIB varies)"""
 import os, sys
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import torch

@@ -5,7 +5,7 @@ import os
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
-LIB_PATH = os.environ.get("UMR_LIB") or os.path.join(_HERE, "lib", "libumr.so")   # UMR_LIB: an instrumented build (tools/probe)
+LIB_PATH = os.environ.get("UMR_LIB") or os.path.join(_HERE, "lib", "libumr.so")   # UMR_LIB: another build of the library (the fenced split-K one: libumr_fence.so)
 CSRC = os.path.join(_HERE, "csrc")
 
 F32, BF16, BF16X3 = 0, 1, 2

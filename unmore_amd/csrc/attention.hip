@@ -272,22 +272,12 @@ __device__ __forceinline__ u32x2 ds_tr_b64(unsigned addr) {
 }
 
 template <int QB>   // 16-query blocks per wave: a workgroup covers 64 * QB queries; K / V^T fragments are read once per QB MFMAs
-#ifndef UMR_ATTN_FWD_MIN_WAVES
-#define UMR_ATTN_FWD_MIN_WAVES 1   // experiment hook (tools/probe/build_exp_lib.sh attention.hip -DUMR_ATTN_FWD_MIN_WAVES=4)
-#endif
-#ifndef UMR_ATTN_DKV_MIN_WAVES
-#define UMR_ATTN_DKV_MIN_WAVES 1
-#endif
-__global__ __launch_bounds__(256, UMR_ATTN_FWD_MIN_WAVES) void attn_fwd_bf16_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
+__global__ __launch_bounds__(256, 1) void attn_fwd_bf16_kernel(const bf16_t* __restrict__ qkv, bf16_t* __restrict__ out,
                                                             float* __restrict__ lse, int N, int heads, int gx_arg) {
     constexpr int TK = 64;                 // keys per tile
     constexpr int OPB = TK * 128;          // one operand tile: 8 KiB
     constexpr int STB = 2 * OPB;           // K | V
-#ifdef UMR_ATTN_PIPE
-    constexpr int RING = 3;                // experiment: QK^T of tile j+1 is issued before the softmax of tile j (needs K[j+1] beside V[j])
-#else
     constexpr int RING = 2;
-#endif
     __shared__ __attribute__((aligned(16))) char smem[RING * STB];
     const int tid = threadIdx.x, lane = tid & 63;
     const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -325,7 +315,7 @@ __global__ __launch_bounds__(256, UMR_ATTN_FWD_MIN_WAVES) void attn_fwd_bf16_ker
     }
     const unsigned tile_stride = (unsigned)(TK * (int)ld * 2);
     auto issue_tile = [&](int j) {
-        char* dst = smem + (RING == 2 ? (j & 1) : (j % RING)) * STB + w * 2048;
+        char* dst = smem + (j & 1) * STB + w * 2048;
         const unsigned so = (unsigned)j * tile_stride;
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsK, UMR_LDS_PTR(dst), 16, voff[0], so, 0, 0);
         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsK, UMR_LDS_PTR(dst + 1024), 16, voff[1], so, 0, 0);
@@ -362,137 +352,12 @@ __global__ __launch_bounds__(256, UMR_ATTN_FWD_MIN_WAVES) void attn_fwd_bf16_ker
     constexpr float DEFER = 8.0f;           // log2 units: raise the running max only when a tile tops it by 2^8
 
     const int ntiles = (N + TK - 1) / TK;
-#ifdef UMR_ATTN_PIPE
-    // ---- experiment: in-wave pipeline.  Iteration j: [tile j+1 landed; barrier] issue tile j+2; S(j+1) = Q K[j+1]^T on the matrix pipe WHILE the
-    // vector unit runs the softmax of S(j); then O += V[j] P(j).  The wave's chain per tile is max(QK^T, softmax) + PV instead of their sum.
-    auto qk_tile = [&](int j, f32x4 (&s)[QB][4]) {
-        const int sb = (j % RING) * STB;
-#pragma unroll
-        for (int sub = 0; sub < 4; ++sub) {
-            const bf16x8 k0 = *(const bf16x8*)(kad0 + sb + sub * 2048);
-            const bf16x8 k1 = *(const bf16x8*)(kad1 + sb + sub * 2048);
-#pragma unroll
-            for (int qi = 0; qi < QB; ++qi) {
-                s[qi][sub] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k0, qf[qi].v[0], f32x4{-m_run[qi], -m_run[qi], -m_run[qi], -m_run[qi]}, 0, 0, 0);
-                s[qi][sub] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(k1, qf[qi].v[1], s[qi][sub], 0, 0, 0);
-            }
-        }
-        if (j == ntiles - 1) {
-#pragma unroll
-            for (int sub = 0; sub < 4; ++sub)
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    if (j * TK + 16 * sub + 4 * g + e >= N) {
-#pragma unroll
-                        for (int qi = 0; qi < QB; ++qi) s[qi][sub][e] = -INFINITY;
-                    }
-        }
-    };
-    f32x4 s[QB][4], sn[QB][4];
     issue_tile(0);
-    if (ntiles > 1) issue_tile(1);
-    if (ntiles > 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    qk_tile(0, s);
-    for (int j = 0; j < ntiles; ++j) {
-        const bool more = j + 1 < ntiles;
-        if (more) {
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();      // tile j+1 landed for everyone; everyone is done with tile j-1's buffer
-            if (j + 2 < ntiles) issue_tile(j + 2);
-            qk_tile(j + 1, sn);                // independent of everything below until the end of the iteration
-        }
-        const int sb = (j % RING) * STB;
-        bool any_up = false;
-        float mxs[QB];
-#pragma unroll
-        for (int qi = 0; qi < QB; ++qi) {
-            float mx = max3f(s[qi][0][0], s[qi][0][1], s[qi][0][2]);
-            mx = max3f(mx, s[qi][0][3], s[qi][1][0]);
-            mx = max3f(mx, s[qi][1][1], s[qi][1][2]);
-            mx = max3f(mx, s[qi][1][3], s[qi][2][0]);
-            mx = max3f(mx, s[qi][2][1], s[qi][2][2]);
-            mx = max3f(mx, s[qi][2][3], s[qi][3][0]);
-            mx = max3f(mx, s[qi][3][1], s[qi][3][2]);
-            mx = max2f(mx, s[qi][3][3]);
-            mx = xor16_max(mx);
-            mx = xor32_max(mx);
-            mxs[qi] = mx;
-            any_up = any_up || (mx > DEFER);
-        }
-        if (j == 0 || __builtin_amdgcn_ballot_w64(any_up) != 0ull) {
-#pragma unroll
-            for (int qi = 0; qi < QB; ++qi) {
-                const float d = (j == 0 || mxs[qi] > DEFER) ? mxs[qi] : 0.f;
-                const float alpha = j == 0 ? 1.0f : __builtin_amdgcn_exp2f(-d);
-                m_run[qi] += d;
-#pragma unroll
-                for (int i = 0; i < 4; ++i) o[qi][i] *= alpha;
-                lacc[qi] *= alpha;
-#pragma unroll
-                for (int sub = 0; sub < 4; ++sub) { s[qi][sub] -= d; if (more) sn[qi][sub] -= d; }   // S(j+1) was started from the old reference
-            }
-        }
-        const unsigned vb0 = (unsigned)sb;
-#pragma unroll
-        for (int half = 0; half < 2; ++half) {
-            u32x2 t0[4], t1[4];
-            if (half == 0) {
-#pragma unroll
-                for (int dt = 0; dt < 4; ++dt) { t0[dt] = ds_tr_b64<0>(vad[dt] + vb0); t1[dt] = ds_tr_b64<2048>(vad[dt] + vb0); }
-            } else {
-#pragma unroll
-                for (int dt = 0; dt < 4; ++dt) { t0[dt] = ds_tr_b64<4096>(vad[dt] + vb0); t1[dt] = ds_tr_b64<4096 + 2048>(vad[dt] + vb0); }
-            }
-            bf16x8 pb[QB];
-#pragma unroll
-            for (int qi = 0; qi < QB; ++qi)
-#pragma unroll
-                for (int e = 0; e < 4; ++e) {
-                    pb[qi][e] = (bf16_t)__builtin_amdgcn_exp2f(s[qi][2 * half][e]);
-                    pb[qi][4 + e] = (bf16_t)__builtin_amdgcn_exp2f(s[qi][2 * half + 1][e]);
-                }
-            asm volatile("s_waitcnt lgkmcnt(0)"
-                         : "+v"(t0[0]), "+v"(t0[1]), "+v"(t0[2]), "+v"(t0[3]), "+v"(t1[0]), "+v"(t1[1]), "+v"(t1[2]), "+v"(t1[3])
-                         :: "memory");
-#pragma unroll
-            for (int dt = 0; dt < 4; ++dt) {
-                const u32x4 f = {t0[dt][0], t0[dt][1], t1[dt][0], t1[dt][1]};
-#pragma unroll
-                for (int qi = 0; qi < QB; ++qi)
-                    o[qi][dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, f), pb[qi], o[qi][dt], 0, 0, 0);
-            }
-#pragma unroll
-            for (int qi = 0; qi < QB; ++qi) lacc[qi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pb[qi], lacc[qi], 0, 0, 0);
-        }
-        if (more) {
-#pragma unroll
-            for (int qi = 0; qi < QB; ++qi)
-#pragma unroll
-                for (int sub = 0; sub < 4; ++sub) s[qi][sub] = sn[qi][sub];
-        }
-    }
-#else
-    issue_tile(0);
-#ifdef UMR_ATTN_BARE
-    // ceiling probe (tools/probe/attn_ceiling.py; never in the product build): both ring buffers are filled ONCE, the tile loop below
-    // then issues no global or LDS-DMA traffic at all -- what is left is the loop's own arithmetic on LDS-resident operands (QK^T MFMAs,
-    // the max3 chain and lane swaps, exp2, bf16 conversion, V^T transposing reads, PV and row-sum MFMAs, one barrier per tile)
-    if (ntiles > 1) issue_tile(1);
-#endif
-#ifdef UMR_ATTN_PEEL_LAST
-    // experiment hook (profiles/r05_attention_experiments.txt): the tile body twice, the key mask only in the copy that runs the last tile
-    auto tile_body = [&](int j, auto last_tag) {
-        constexpr bool LAST = decltype(last_tag)::value;
-#else
     for (int j = 0; j < ntiles; ++j) {
         const bool LAST = j == ntiles - 1;
-#endif
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();          // tile j landed for everyone; everyone is done reading buffer (j+1)&1
-#ifndef UMR_ATTN_BARE
         if (!LAST) issue_tile(j + 1);
-#endif
         const int sb = (j & 1) * STB;
         // S^T tiles: 4 x (16 keys x 16 queries) per query block
         f32x4 s[QB][4];
@@ -585,14 +450,7 @@ __global__ __launch_bounds__(256, UMR_ATTN_FWD_MIN_WAVES) void attn_fwd_bf16_ker
 #pragma unroll
             for (int qi = 0; qi < QB; ++qi) lacc[qi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pb[qi], lacc[qi], 0, 0, 0);
         }
-#ifdef UMR_ATTN_PEEL_LAST
-    };
-    for (int j = 0; j < ntiles - 1; ++j) tile_body(j, std::false_type{});
-    tile_body(ntiles - 1, std::true_type{});
-#else
     }
-#endif
-#endif   // UMR_ATTN_PIPE
 #pragma unroll
     for (int qi = 0; qi < QB; ++qi) {
         const int q = q0 + 16 * qi;
@@ -1051,7 +909,7 @@ __device__ __forceinline__ void attn_bwd_dkv_bf16_body(char* smem, const bf16_t*
 }
 
 template <int KB>
-__global__ __launch_bounds__(256, UMR_ATTN_DKV_MIN_WAVES) void attn_bwd_dkv_bf16_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
+__global__ __launch_bounds__(256, 1) void attn_bwd_dkv_bf16_kernel(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ dout,
                                                                 const float* __restrict__ ws, bf16_t* __restrict__ dqkv, int N,
                                                                 int Npad, int heads, int gx_arg) {
     __shared__ __attribute__((aligned(16))) char smem[4 * 64 * 128 + 2 * 1024];
@@ -1205,31 +1063,19 @@ extern "C" int umr_attention_fwd(const void* qkv, void* out, float* lse, int B, 
     UMR_CHECK_ARG(B > 0 && N > 0 && heads > 0, "attention_fwd: empty problem");
     if (head_dim != HD) return umr_set_error(UMR_ERR_UNSUPPORTED, "attention: head_dim must be 64");
     hipStream_t s = (hipStream_t)stream;
-    // 1-D grids of gx x (B * heads) workgroups; the kernels map their id XCD-aware (attn_block).  UMR_ATTN_XCD=0: the old order
-    static const int xcd_map = umr_env_int("UMR_ATTN_XCD", 1);
+    // 1-D grids of gx x (B * heads) workgroups; the kernels map their id XCD-aware (attn_block)
     const int gx1 = (N + 63) / 64, gx2 = (N + 127) / 128;
     UMR_CHECK_ARG((int64_t)gx1 * B * heads < (1ll << 31), "attention_fwd: grid too large");
     dim3 g((unsigned)(gx1 * B * heads)), b(256);
-    const int a1 = xcd_map ? gx1 : -gx1, a2 = xcd_map ? gx2 : -gx2;
-    static const int fast_fwd = umr_env_int("UMR_ATTN_FAST", 1);   // 0: the generic kernel for bf16 too (A/B)
-    if (dtype == UMR_BF16 && fast_fwd) {
-        if (N >= 128 && fast_fwd != 2) {   // 32 queries per wave: half the LDS reads per MFMA
+    if (dtype == UMR_BF16) {
+        if (N >= 128) {   // 32 queries per wave: half the LDS reads per MFMA
             dim3 g2((unsigned)(gx2 * B * heads));
-#ifdef UMR_ATTN_BARE
-            // probe build only: extra dynamic LDS per workgroup caps the resident workgroups per CU (32 KiB static: 0 -> 4 per CU by
-            // registers, 24576 -> 2, 98304 -> 1): the bare loop at 4, 2 and 1 waves per SIMD
-            static const int pad = umr_env_int("UMR_ATTN_BARE_LDS", 0);
-            if (pad > 0) (void)hipFuncSetAttribute((const void*)attn_fwd_bf16_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, pad);
-            hipLaunchKernelGGL(attn_fwd_bf16_kernel<2>, g2, b, pad, s, (const bf16_t*)qkv, (bf16_t*)out, lse, N, heads, a2);
-#else
-            hipLaunchKernelGGL(attn_fwd_bf16_kernel<2>, g2, b, 0, s, (const bf16_t*)qkv, (bf16_t*)out, lse, N, heads, a2);
-#endif
+            hipLaunchKernelGGL(attn_fwd_bf16_kernel<2>, g2, b, 0, s, (const bf16_t*)qkv, (bf16_t*)out, lse, N, heads, gx2);
         } else {
-            hipLaunchKernelGGL(attn_fwd_bf16_kernel<1>, g, b, 0, s, (const bf16_t*)qkv, (bf16_t*)out, lse, N, heads, a1);
+            hipLaunchKernelGGL(attn_fwd_bf16_kernel<1>, g, b, 0, s, (const bf16_t*)qkv, (bf16_t*)out, lse, N, heads, gx1);
         }
     }
-    else if (dtype == UMR_BF16) hipLaunchKernelGGL(attn_fwd_kernel<bf16_t>, g, b, 0, s, (const bf16_t*)qkv, (bf16_t*)out, lse, N, heads, a1);
-    else if (dtype == UMR_F32) hipLaunchKernelGGL(attn_fwd_kernel<float>, g, b, 0, s, (const float*)qkv, (float*)out, lse, N, heads, a1);
+    else if (dtype == UMR_F32) hipLaunchKernelGGL(attn_fwd_kernel<float>, g, b, 0, s, (const float*)qkv, (float*)out, lse, N, heads, gx1);
     else return umr_set_error(UMR_ERR_INVALID, "attention_fwd: dtype");
     UMR_LAUNCH_CHECK();
     return UMR_OK;
@@ -1247,40 +1093,33 @@ extern "C" int umr_attention_bwd(const void* qkv, const void* out, const void* d
     if (head_dim != HD) return umr_set_error(UMR_ERR_UNSUPPORTED, "attention: head_dim must be 64");
     hipStream_t s = (hipStream_t)stream;
     const int64_t total = (int64_t)B * N * heads;
-    static const int xcd_map = umr_env_int("UMR_ATTN_XCD", 1);
     const int gx1 = (N + 63) / 64, gx2 = (N + 127) / 128;
     UMR_CHECK_ARG((int64_t)gx1 * B * heads < (1ll << 31), "attention_bwd: grid too large");
-    const int a1 = xcd_map ? gx1 : -gx1, a2 = xcd_map ? gx2 : -gx2;
     dim3 gp((unsigned)((total + 255) / 256)), g((unsigned)(gx1 * B * heads)), b(256);
-    static const int fast_bwd = umr_env_int("UMR_ATTN_FAST", 1);   // 0: the generic kernels for bf16 too (A/B)
     // short sequences: one launch (dQ and dK / dV workgroups side by side, no prep pass).  UMR_ATTN_BWD_FUSED=0: the three launches (A/B;
     // umr_set_debug_option)
-    if (dtype == UMR_BF16 && fast_bwd && N < 128 && umr_opt_or(UMR_OPT_ATTN_BWD_FUSED, 1) != 0) {
+    if (dtype == UMR_BF16 && N < 128 && umr_opt_or(UMR_OPT_ATTN_BWD_FUSED, 1) != 0) {
         const int half = gx1 * B * heads;
         UMR_CHECK_ARG(2ll * half < (1ll << 31), "attention_bwd: grid too large");
         hipLaunchKernelGGL(attn_bwd_small_bf16_kernel, dim3((unsigned)(2 * half)), b, 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, (const bf16_t*)out,
-                           lse, (bf16_t*)dqkv, N, heads, a1, half);
-    } else if (dtype == UMR_BF16 && fast_bwd) {
+                           lse, (bf16_t*)dqkv, N, heads, gx1, half);
+    } else if (dtype == UMR_BF16) {
         const int Npad = (N + 63) / 64 * 64;
         const int64_t tp = (int64_t)B * heads * Npad * 8;
         hipLaunchKernelGGL(attn_bwd_prep_bf16_kernel, dim3((unsigned)((tp + 255) / 256)), b, 0, s, (const bf16_t*)out, (const bf16_t*)dout, lse,
                            dsum_ws, B, N, Npad, heads);
-        if (N >= 128 && fast_bwd != 2) {
+        if (N >= 128) {
             dim3 g2((unsigned)(gx2 * B * heads));
-            hipLaunchKernelGGL(attn_bwd_dq_bf16_kernel<2>, g2, b, 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, dsum_ws, (bf16_t*)dqkv, N, Npad, heads, a2);
-            hipLaunchKernelGGL(attn_bwd_dkv_bf16_kernel<2>, g2, b, 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, dsum_ws, (bf16_t*)dqkv, N, Npad, heads, a2);
+            hipLaunchKernelGGL(attn_bwd_dq_bf16_kernel<2>, g2, b, 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, dsum_ws, (bf16_t*)dqkv, N, Npad, heads, gx2);
+            hipLaunchKernelGGL(attn_bwd_dkv_bf16_kernel<2>, g2, b, 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, dsum_ws, (bf16_t*)dqkv, N, Npad, heads, gx2);
         } else {
-            hipLaunchKernelGGL(attn_bwd_dq_bf16_kernel<1>, g, b, 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, dsum_ws, (bf16_t*)dqkv, N, Npad, heads, a1);
-            hipLaunchKernelGGL(attn_bwd_dkv_bf16_kernel<1>, g, b, 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, dsum_ws, (bf16_t*)dqkv, N, Npad, heads, a1);
+            hipLaunchKernelGGL(attn_bwd_dq_bf16_kernel<1>, g, b, 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, dsum_ws, (bf16_t*)dqkv, N, Npad, heads, gx1);
+            hipLaunchKernelGGL(attn_bwd_dkv_bf16_kernel<1>, g, b, 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, dsum_ws, (bf16_t*)dqkv, N, Npad, heads, gx1);
         }
-    } else if (dtype == UMR_BF16) {
-        hipLaunchKernelGGL(attn_bwd_prep_kernel<bf16_t>, gp, b, 0, s, (const bf16_t*)out, (const bf16_t*)dout, dsum_ws, B, N, heads);
-        hipLaunchKernelGGL(attn_bwd_dq_kernel<bf16_t>, g, b, 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse, dsum_ws, (bf16_t*)dqkv, N, heads, a1);
-        hipLaunchKernelGGL(attn_bwd_dkv_kernel<bf16_t>, g, b, 0, s, (const bf16_t*)qkv, (const bf16_t*)dout, lse, dsum_ws, (bf16_t*)dqkv, N, heads, a1);
     } else if (dtype == UMR_F32) {
         hipLaunchKernelGGL(attn_bwd_prep_kernel<float>, gp, b, 0, s, (const float*)out, (const float*)dout, dsum_ws, B, N, heads);
-        hipLaunchKernelGGL(attn_bwd_dq_kernel<float>, g, b, 0, s, (const float*)qkv, (const float*)dout, lse, dsum_ws, (float*)dqkv, N, heads, a1);
-        hipLaunchKernelGGL(attn_bwd_dkv_kernel<float>, g, b, 0, s, (const float*)qkv, (const float*)dout, lse, dsum_ws, (float*)dqkv, N, heads, a1);
+        hipLaunchKernelGGL(attn_bwd_dq_kernel<float>, g, b, 0, s, (const float*)qkv, (const float*)dout, lse, dsum_ws, (float*)dqkv, N, heads, gx1);
+        hipLaunchKernelGGL(attn_bwd_dkv_kernel<float>, g, b, 0, s, (const float*)qkv, (const float*)dout, lse, dsum_ws, (float*)dqkv, N, heads, gx1);
     } else return umr_set_error(UMR_ERR_INVALID, "attention_bwd: dtype");
     UMR_LAUNCH_CHECK();
     return UMR_OK;

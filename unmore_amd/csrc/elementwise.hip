@@ -784,12 +784,7 @@ __global__ __launch_bounds__(256) void head_out_bwd_kernel(const T* __restrict__
 // owns one 512-column half of a run of 64 consecutive rows: lane l first fetches the gradient pair of row l (coalesced), the row
 // loop broadcasts it with v_readlane and keeps HOB_UNROLL 16-byte loads per lane in flight.  Waves (half, stream) = (wv & 1,
 // wv >> 1); the two row streams of a block are added in a fixed order through LDS, so the partial slab keeps its layout.
-#ifndef HOB_UNROLL
-#define HOB_UNROLL 2
-#endif
-#ifndef HOB_NT
-#define HOB_NT 0
-#endif
+constexpr int HOB_UNROLL = 2;
 __global__ __launch_bounds__(256) void head_out_bwd_k1024_kernel(const bf16_t* __restrict__ h, const float* __restrict__ w,
                                                                  const float* __restrict__ dout, const float* __restrict__ yout,
                                                                  bf16_t* __restrict__ dh, float* __restrict__ part, int64_t M, int Cout,
@@ -837,22 +832,14 @@ __global__ __launch_bounds__(256) void head_out_bwd_k1024_kernel(const bf16_t* _
                 a0[j] += hv * g0;
                 a1[j] += hv * g1;
             }
-#if HOB_NT & 2
-            __builtin_nontemporal_store(__builtin_bit_cast(f32x4, o), (f32x4*)(dp + (int64_t)i * K));
-#else
             *(bf16x8*)(dp + (int64_t)i * K) = o;
-#endif
         };
         int i = 0;
         for (; i + HOB_UNROLL <= n; i += HOB_UNROLL) {
             bf16x8 t[HOB_UNROLL];
 #pragma unroll
             for (int u = 0; u < HOB_UNROLL; ++u) {
-#if HOB_NT & 1
-                t[u] = __builtin_bit_cast(bf16x8, __builtin_nontemporal_load((const f32x4*)(hp + (int64_t)(i + u) * K)));
-#else
                 t[u] = *(const bf16x8*)(hp + (int64_t)(i + u) * K);
-#endif
             }
 #pragma unroll
             for (int u = 0; u < HOB_UNROLL; ++u) row(t[u], i + u);

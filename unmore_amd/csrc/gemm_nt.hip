@@ -248,7 +248,6 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const umr_gemm_desc p, 
             }
             return;
         }
-#ifndef UMR_NT_FRAGS_PER_KSTEP   // (A/B hook: the round-4 form below, fragments read per 32-wide k-step)
         if constexpr (sizeof(T) == 2) {
             // bf16: all 16 fragment reads of the K-tile are issued before its first MFMA -- one exposed LDS latency per K-tile instead of one per
             // group of reads the compiler's schedule waited for (+32 VGPRs, still two workgroups per CU).  With two workgroups on a CU
@@ -272,36 +271,22 @@ __global__ __launch_bounds__(256, 2) void gemm_nt_kernel(const umr_gemm_desc p, 
                         acc[mt][ntl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[ks][ntl], af[ks][mt], acc[mt][ntl], 0, 0, 0);
             return;
         }
-#endif
+        // fp32: fragments read per 32-wide k-step
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            if constexpr (sizeof(T) == 2) {
-                bf16x8 af[4], bfr[4];
+            f32x4 af[4], bfr[4];
 #pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    af[i] = *(const bf16x8*)(sbuf + a_addr[ks][i]);
-                    bfr[i] = *(const bf16x8*)(sbuf + b_addr[ks][i]);
-                }
+            for (int i = 0; i < 4; ++i) {
+                af[i] = *(const f32x4*)(sbuf + a_addr[ks][i]);
+                bfr[i] = *(const f32x4*)(sbuf + b_addr[ks][i]);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
 #pragma unroll
                 for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
                     for (int ntl = 0; ntl < 4; ++ntl)
-                        acc[mt][ntl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(bfr[ntl], af[mt], acc[mt][ntl], 0, 0, 0);
-            } else {
-                f32x4 af[4], bfr[4];
-#pragma unroll
-                for (int i = 0; i < 4; ++i) {
-                    af[i] = *(const f32x4*)(sbuf + a_addr[ks][i]);
-                    bfr[i] = *(const f32x4*)(sbuf + b_addr[ks][i]);
-                }
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-#pragma unroll
-                    for (int mt = 0; mt < 4; ++mt)
-#pragma unroll
-                        for (int ntl = 0; ntl < 4; ++ntl)
-                            acc[mt][ntl] = __builtin_amdgcn_mfma_f32_16x16x4f32(bfr[ntl][j], af[mt][j], acc[mt][ntl], 0, 0, 0);
-            }
+                        acc[mt][ntl] = __builtin_amdgcn_mfma_f32_16x16x4f32(bfr[ntl][j], af[mt][j], acc[mt][ntl], 0, 0, 0);
         }
     };
 
@@ -546,11 +531,11 @@ static bool uses_256(const umr_gemm_desc* d) {
     const bool kfit = d->conv == 0 ? (d->K % 64 == 0) : (d->Cin % 64 == 0);  // the 256 kernel has no K-tail path
     // >= 8 full rounds of one 256x256 tile per CU (no tail, overheads amortised); plain GEMMs already win from 1.5 rounds on
     // when K >= 512 or there are >= 4 rounds (the transformer's GEMMs at 37 k tokens: tools/vit_block_bench.py)
-    // UMR_NT256_MIN_TILES: smallest plain-GEMM problem (in 256x256 tiles) given to the 256x256 kernel
-    static const int min_tiles = umr_env_int("UMR_NT256_MIN_TILES", 300);   // 384 -> 300: +2 % on the ViT-L/14 step (proj / fc2 at 344 tiles), neutral at cfg2
+    // smallest plain-GEMM problem (in 256x256 tiles) given to the 256x256 kernel
+    constexpr int min_tiles = 300;   // 384 -> 300: +2 % on the ViT-L/14 step (proj / fc2 at 344 tiles), neutral at cfg2
     // smallest 3x3-conv problem on the 256x256 kernel: its K loop is 9 x Cin long, so two to three rounds of tiles already beat
     // the 128x128 kernel (cfg1's head convs, 784 tiles: 542 -> 577 images/s; cfg2 / cfg4 / ref / the sweep unchanged)
-    static const int conv_min_tiles = umr_env_int("UMR_NT256_CONV_MIN_TILES", 512);
+    constexpr int conv_min_tiles = 512;
     const bool big = kfit && d->N >= 192 &&
                      (t256 >= 2048 || (d->conv == 1 && t256 >= conv_min_tiles) || (d->conv == 0 && d->a_rows_in <= 0 && t256 >= min_tiles && (d->K >= 512 || t256 >= 1024)));
     return kfit && (ov == 256 || (ov == 0 && big));

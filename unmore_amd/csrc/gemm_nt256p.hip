@@ -107,20 +107,12 @@ __global__ __launch_bounds__(512, 2) void gemm_nt256p_kernel(const umr_gemm_desc
     // barrier wait sits beside the other half's MFMAs.  Both halves read a phase's data in the same interval and issue the
     // same LDS-DMA groups in the same interval (the ahead half carries in its MFMA block the groups the other half issues
     // in the block it runs meanwhile), so LDS lifetimes, counted vmcnt waits and barrier counts are unchanged.
-#ifdef UMR_EXP_AHEAD_HI
-    const bool ahead = (stagger != 0) && (w >= 4);
-#else
     const bool ahead = (stagger != 0) && (w < 4);
-#endif
 
     // tile sequence of this workgroup: virtual ids pw, pw + G, pw + 2G, ...; workgroups of one XCD (blockIdx % 8)
     // own a contiguous run of G/8 ids per round, so neighbouring tiles share that XCD's L2
     const int G = gridDim.x;
-#ifdef UMR_EXP_NO_XCD_REMAP   // experiment (tools/probe/xcd_remap_fetch.sh): consecutive tiles on consecutive workgroups = on different XCDs
-    const int pw = (int)blockIdx.x;
-#else
     const int pw = ((G & 7) == 0) ? (int)(blockIdx.x & 7) * (G >> 3) + (int)(blockIdx.x >> 3) : (int)blockIdx.x;
-#endif
     if (pw >= total_tiles) return;
     const int n_my = (total_tiles - pw + G - 1) / G;
 
@@ -217,7 +209,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt256p_kernel(const umr_gemm_desc
         // X3: planes of this K-tile's pair, 2 bits per pair
         // pairs ordered so that equal A planes are consecutive -- (h,h) (h,m) (h,l) (m,h) (m,m) (l,h): the second and third
         // read of an A-plane tile come 1.5 us after the first and hit L2 (+1.8 % on the head conv against the order that
-        // alternated planes, tools/probe/x3_order_ab.sh); three-term mode: (h,h) (h,m) (m,h)
+        // alternated planes); three-term mode: (h,h) (h,m) (m,h)
         const int pa = X3 ? (((npairs == 6 ? 0x940 : 0x010) >> (2 * st_pp)) & 3) : 0;   // A planes 0,0,0,1,1,2  |  0,0,1
         const int pb = X3 ? (((npairs == 6 ? 0x124 : 0x004) >> (2 * st_pp)) & 3) : 0;   // B planes 0,1,2,0,1,0  |  0,1,0
         const bool next_k = !X3 || st_pp == npairs - 1;
@@ -273,14 +265,11 @@ __global__ __launch_bounds__(512, 2) void gemm_nt256p_kernel(const umr_gemm_desc
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");             \
     __builtin_amdgcn_sched_barrier(0);
 #define MFMA(ACC, BF, AF) ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(BF, AF, ACC, 0, 0, 0)
-#ifndef UMR_EXP_PRIO_MODE
-#define UMR_EXP_PRIO_MODE 1
-#endif
-    // priority policy of the MFMA clusters: 0 = raise around every cluster (flips); 1 / 2 = static priority 1 for waves 4-7 /
-    // waves 0-3 and no flips; 3 = none.  Measured on the head conv (two-phase K-tile, same box, tools/probe/prio_ab.sh): 30.9 /
-    // 30.2 / 31.1 / 31.2 ms -- the guide's "static priority for the younger half" (Two waves per SIMD, item 4).  The four-phase
-    // plain GEMMs lose 4-10 % without the flips (their LDS-DMA pieces are issued inside the raised cluster) and keep them.
-    constexpr int PRIO_MODE = P2 ? UMR_EXP_PRIO_MODE : 0;
+    // priority policy of the MFMA clusters: 0 = raise around every cluster (flips); 1 = static priority 1 for waves 4-7 and no
+    // flips.  Measured on the head conv (two-phase K-tile, same box): 30.9 ms with flips, 30.2 with the static priority for waves
+    // 4-7, 31.1 for waves 0-3, 31.2 with none -- the guide's "static priority for the younger half" (Two waves per SIMD, item 4).
+    // The four-phase plain GEMMs lose 4-10 % without the flips (their LDS-DMA pieces are issued inside the raised cluster) and keep them.
+    constexpr int PRIO_MODE = P2 ? 1 : 0;
 #define QPRIO(x) if (PRIO_MODE == 0) __builtin_amdgcn_s_setprio(x);
 #define QUADRANT_D(M0, N0, FB, DMA_A, DMA_B)                                                         \
     QPRIO(1)                                                                                        \
@@ -347,17 +336,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt256p_kernel(const umr_gemm_desc
     //   P1(t) issues A0,B0,B1 of tile t+2 (their regions were last read in P0(t)),  P0(t+1) issues A1 of tile t+2;
     //   wait of P1(t): A0,B0,B1(t+1) landed, A1(t+1) may fly -> vmcnt(2);  wait of P0(t): A1(t) landed, A0,B0,B1(t+1) may
     //   fly -> vmcnt(6).  Every group has one K-tile (two phases) to land.
-#ifdef UMR_NT256P_TIMESTAMPS
-    const bool dbg = (p.rows_per_batch == -9) && blockIdx.x == 0 && tid == 0;
-    unsigned long long* dbgp = (unsigned long long*)p.rowbias;
-    bool ph_rec = false;   // stamps inside one K-tile (4-phase form): slots 128..135
-    // slots 136..139: shader-clock and 100-MHz real-time stamps around the whole kernel -> the clock the chip holds under
-    // this load = d(s_memtime) / d(s_memrealtime) x 100 MHz (MI355X_MICROARCH.md, DVFS give-back item 6; tools/power_probe.py)
-    if (dbg) { dbgp[136] = __builtin_readcyclecounter(); dbgp[137] = __builtin_amdgcn_s_memrealtime(); }
-#define PT(k) do { if (dbg && ph_rec) dbgp[128 + (k)] = __builtin_readcyclecounter(); } while (0)
-#else
-#define PT(k) do { } while (0)
-#endif
     auto tile_body2 = [&](const char* sbuf) {
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
@@ -390,30 +368,22 @@ __global__ __launch_bounds__(512, 2) void gemm_nt256p_kernel(const umr_gemm_desc
             for (int i = 0; i < 4; ++i) fa[ks][i] = A_FRAG(ks, i);
         }
         PHASE_SYNC();
-        PT(0);
         QUADRANT(0, 0, fb0, 2)
-        PT(1);
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
             for (int i = 0; i < 2; ++i) fb1[ks][i] = B_FRAG(ks, 2 + i);
         PHASE_SYNC();
-        PT(2);
         QUADRANT(0, 2, fb1, 3)
-        PT(3);
         stage_prep();
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks)
 #pragma unroll
             for (int i = 0; i < 4; ++i) fa[ks][i] = A_FRAG(ks, 4 + i);
         PHASE_SYNC();
-        PT(4);
         QUADRANT_HI(2, fb1, 0)
-        PT(5);
         PHASE_SYNC();
-        PT(6);
         QUADRANT_HI(0, fb0, 1)
-        PT(7);
     };
 
 #define READ_WAIT()                                                \
@@ -479,7 +449,6 @@ __global__ __launch_bounds__(512, 2) void gemm_nt256p_kernel(const umr_gemm_desc
     };
 
     if (PRIO_MODE == 1 && w >= 4) __builtin_amdgcn_s_setprio(1);
-    if (PRIO_MODE == 2 && w < 4) __builtin_amdgcn_s_setprio(1);
     // prologue: the six groups the steady-state schedule has already issued when the first K-tile starts
     stage_setup(0);
     stage_prep();
@@ -541,21 +510,12 @@ __global__ __launch_bounds__(512, 2) void gemm_nt256p_kernel(const umr_gemm_desc
         }
     };
     if (BIAS_INIT) fetch_bias(0);
-    // -DUMR_NT256P_TIMESTAMPS (tools/probe/ts_probe.py builds its own library with it): workgroup 0 / thread 0 writes
-    // s_memtime stamps of the first 16 tiles to the rowbias pointer when rows_per_batch == -9 -- how the per-tile budget was taken apart
-#ifdef UMR_NT256P_TIMESTAMPS
-#define TS(slot) do { if (dbg && it < 16) dbgp[it * 8 + (slot)] = __builtin_readcyclecounter(); } while (0)
-#else
-#define TS(slot) do { } while (0)
-#endif
 #pragma unroll 1
     for (int it = 0; it < n_my; ++it) {
-        TS(0);
 #pragma unroll
         for (int i = 0; i < 8; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[i][j] = BIAS_INIT ? bqn[j] : f32x4{0.f, 0.f, 0.f, 0.f};
-        TS(1);
         if (RED && w < 2) {
             // reduction weights of this tile's 256 columns: row c = w of red_w as one 1-KiB LDS-DMA (columns >= N and a
             // missing second row read as zeros)
@@ -577,18 +537,10 @@ __global__ __launch_bounds__(512, 2) void gemm_nt256p_kernel(const umr_gemm_desc
         } else {
 #pragma unroll 1
             for (int t = 0; t < nt; ++t) {
-#ifdef UMR_NT256P_TIMESTAMPS
-                ph_rec = (it == 4 && t == 5);
-#endif
                 tile_body(smem + c_par * BUF2);
                 c_par ^= 1;
-#ifdef UMR_NT256P_TIMESTAMPS
-                if (t == 0) TS(2);
-                if (t == 1) TS(3);
-#endif
             }
         }
-        TS(4);
         // ---- epilogue of output tile `it`; the next tile's first K-tiles are already in flight
         const int v = it * G + pw;
         const int tm = v / tiles_n, tn = v - tm * tiles_n;
@@ -756,11 +708,7 @@ __global__ __launch_bounds__(512, 2) void gemm_nt256p_kernel(const umr_gemm_desc
                             for (int e = 0; e < 4; ++e) o[k][e] = add_bf16x2(o[k][e], a[e]);
                         }
                         const unsigned so = (unsigned)(((MB + mh) * 16 + k * 8) * p.ldc * 2);
-#ifdef UMR_EXP_NT_STORE   // experiment (tools/energy_probe.py): non-temporal C stores -- C is re-read only by a much later kernel
-                        __builtin_amdgcn_raw_buffer_store_b128(o[k], rsC, co_vo + so, 0, 2);
-#else
                         __builtin_amdgcn_raw_buffer_store_b128(o[k], rsC, co_vo + so, 0, 0);
-#endif
                     }
                 }
             };
@@ -781,11 +729,9 @@ __global__ __launch_bounds__(512, 2) void gemm_nt256p_kernel(const umr_gemm_desc
                     row_reduce2(tq[0][0], tq[0][1], tq[1][0], tq[1][1], mt);
                 }
             } else {
-                blocks2(std::integral_constant<int, 0>{}); TS(5); blocks2(std::integral_constant<int, 2>{});
+                blocks2(std::integral_constant<int, 0>{}); blocks2(std::integral_constant<int, 2>{});
                 blocks2(std::integral_constant<int, 4>{}); blocks2(std::integral_constant<int, 6>{});
             }
-            TS(6);
-            TS(7);
         } else if (EPI == 4) {
             // GELU class (the transformer MLP): act == GELU with the pre-activation optionally saved to C2 (c2_mode 2), or
             // the GELU'-masked gradient (MASK_DGELU).  Same bf16 staging as the fast class, in its own instantiation so that
@@ -1008,16 +954,11 @@ __global__ __launch_bounds__(512, 2) void gemm_nt256p_kernel(const umr_gemm_desc
     }
     // the trailing (zero-fill) LDS-DMA groups must land before the LDS allocation is released
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifdef UMR_NT256P_TIMESTAMPS
-    if (dbg) { dbgp[138] = __builtin_readcyclecounter(); dbgp[139] = __builtin_amdgcn_s_memrealtime(); }
-#endif
 #undef QUADRANT
 #undef QUADRANT_S
 #undef QUADRANT_HI
 #undef QUADRANT_HID
 #undef QUADRANT_SD
-#undef TS
-#undef PT
 #undef QUADRANT_D
 #undef MFMA
 #undef PHASE_SYNC
@@ -1090,7 +1031,6 @@ static bool umr_nt256p_gelu_epilogue(const umr_gemm_desc* d) {
 static void x3_plan(const umr_gemm_desc* d, int cus, int npairs, int64_t ws_bytes, int* bm_out, int* ks_out) {
     const int tiles_n = (d->N + BN2 - 1) / BN2;
     const int kt = d->conv == 0 ? d->K / BK2 : 9 * (d->Cin / BK2);
-    static const int forced = umr_env_int("UMR_X3_KSPLIT", 0);   // 0 = cost model; n = at most n runs (1 disables)
     const int bm_env = umr_opt_or(UMR_OPT_NT256_BM, 0);          // tests switch it inside one process (umr_set_debug_option)
     const int64_t slab = (int64_t)d->M * d->N * 4;
     int best_ks = 1, best_bm = BM2;
@@ -1100,7 +1040,6 @@ static void x3_plan(const umr_gemm_desc* d, int cus, int npairs, int64_t ws_byte
         const int64_t tiles = (int64_t)((d->M + bm - 1) / bm) * tiles_n;
         for (int ks = 1; ks <= 32 && ks * 2 <= kt + 1; ++ks) {
             if (d->red_w && ks > 1) break;
-            if (forced > 0 && ks > forced) break;
             if (ks > 1 && ((int64_t)ks * slab > ws_bytes)) break;
             const int per = (kt + ks - 1) / ks;
             if ((kt + per - 1) / per != ks) continue;            // no empty run
@@ -1139,7 +1078,7 @@ int umr_launch_gemm_nt256p_ws(const umr_gemm_desc* d, void* ws, int64_t ws_bytes
     // rows per tile (see the kernel): for plain GEMMs of a few rounds, the bm in {256, 224, 192} with the smallest
     // rounds x tile time (tile time ~ a fixed quarter -- epilogue, first-load latency -- plus the K loop, which scales with bm);
     // the waves that skip blocks are the non-ahead half, so the stagger has to be on.  UMR_NT256_BM forces a value.
-    static const int stagger = umr_env_int("UMR_NT256_STAGGER", 1);   // A/B switch (0 = all waves in lock-step)
+    constexpr int stagger = 1;   // waves 0-3 run ahead of waves 4-7 (see the kernel)
     const int bm_env = umr_opt_or(UMR_OPT_NT256_BM, 0);   // tests switch it inside one process (umr_set_debug_option)
     int bm = BM2;
     if (d->conv == 0 && d->dtype == UMR_BF16) {
@@ -1166,9 +1105,8 @@ int umr_launch_gemm_nt256p_ws(const umr_gemm_desc* d, void* ws, int64_t ws_bytes
     // a one-workgroup-per-CU launch would leave the workgroups that did not get a CU to run a second full round after the
     // others -- up to 2x the kernel time.  With several shorter workgroups per CU the dispatcher balances them itself; a
     // workgroup still walks >= 32 tiles, so the cross-tile prefetch keeps its value, and workgroups that run together on
-    // one XCD still own neighbouring tiles (pw in the kernel).  UMR_NT256_WG_PER_CU overrides the factor.
-    static const int wg_per_cu = umr_env_int("UMR_NT256_WG_PER_CU", 0);
-    int64_t kf = wg_per_cu > 0 ? wg_per_cu : total / ((int64_t)cus * 32);
+    // one XCD still own neighbouring tiles (pw in the kernel).
+    int64_t kf = total / ((int64_t)cus * 32);
     if (kf < 1) kf = 1;
     if (kf > 8) kf = 8;
     // CU budget (umr_set_cu_budget): exactly `budget` workgroups, one per CU -- the other CUs stay free for a collective's kernels.

@@ -445,11 +445,9 @@ TnPlan tn_plan(const umr_gemm_tn_desc* d) {
     // weight-gradient lane of that step is bound by its traffic and by the chip it shares with the data-gradient chain, not by one
     // launch's latency: three splits of every weight (the rule above) wrote and re-read 8 GB of slabs per step; with ~256 workgroups
     // per launch the 192- and 256-tile weights take one split (and no reduce pass, below), the 64-tile ones four
-    // (same box: 922.5 -> 945 images/s; UMR_TN_PLAN=<workgroups> to try another target, =-1 the old rule)
-    static const int plan_env = [] { const char* e = getenv("UMR_TN_PLAN"); return e ? atoi(e) : 0; }();
-    if (plan_env >= 0 && d->M <= 4096) {
-        const int target = plan_env > 0 ? plan_env : 256;
-        want = (target + tiles / 2) / tiles;
+    // (same box: 922.5 -> 945 images/s)
+    if (d->M <= 4096) {
+        want = (256 + tiles / 2) / tiles;
         max_by_rows = ((int64_t)d->M + rows * 4 - 1) / (rows * 4);
     }
     if (want > max_by_rows) want = max_by_rows;

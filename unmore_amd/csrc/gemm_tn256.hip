@@ -258,12 +258,10 @@ __global__ __launch_bounds__(512, 2) void gemm_tn256_kernel(const umr_gemm_tn_de
     __builtin_amdgcn_sched_barrier(0);
     // D[i = k_local][j = n_local] = sum_m X[m,k] dY[m,n]: first operand = X fragment, second = dY fragment
 #define MFMA(ACC, XF, YF) ACC = __builtin_amdgcn_mfma_f32_16x16x32_bf16(XF, YF, ACC, 0, 0, 0)
-#ifndef UMR_EXP_TN_PRIO_MODE
-#define UMR_EXP_TN_PRIO_MODE 1   // conv weight gradient, same box: 33.7 / 33.2 / 33.4 ms for modes 0 / 1 / 3
-#endif
-    // static priority for waves 4-7 in the two-phase form, as in gemm_nt256p.hip; round 4: for the plain weight gradients as well
+    // static priority for waves 4-7 in the two-phase form, as in gemm_nt256p.hip (conv weight gradient, same box: 33.7 ms with the
+    // flips, 33.2 with the static priority, 33.4 with none); round 4: for the plain weight gradients as well
     // (about -1 %: 1x1 head 7.81 -> 7.73 ms, ViT-B fc1 182.6 -> 174.0 us; profiles/r04_plain_gemm_two_phase_ab.txt)
-    constexpr int PRIO_MODE = PH2 ? UMR_EXP_TN_PRIO_MODE : 0;
+    constexpr int PRIO_MODE = PH2 ? 1 : 0;
 #define QPRIO(x) if (PRIO_MODE == 0) __builtin_amdgcn_s_setprio(x);
 #define QUADRANT_D(N0, K0, FX, DMA_A, DMA_B)                                                         \
     QPRIO(1)                                                                                        \
@@ -417,7 +415,6 @@ bool umr_tn256_eligible(const umr_gemm_tn_desc* d, bool force) {
 
 void umr_tn256_plan(const umr_gemm_tn_desc* d, int* splits, int* rows_per_split) {
     const int64_t tiles = (int64_t)((d->N + 255) / 256) * ((d->K + 255) / 256);
-    static const int rounds_env = umr_env_int("UMR_TN256_ROUNDS", -1);
     // Rounds of one workgroup per CU: every split writes a 256 KiB fp32 partial per tile and the reduction reads it back,
     // so few-row problems (the transformer weight gradients: 37 k tokens) want ONE round of long splits -- 4 rounds cost
     // +50 % there (tools/vit_block_bench.py) -- while the pixel-sized ones (>= 64 stages per split even at 4 rounds) keep
@@ -426,7 +423,6 @@ void umr_tn256_plan(const umr_gemm_tn_desc* d, int* splits, int* rows_per_split)
     int64_t rounds = (int64_t)d->M * tiles * x3 / (256ll * 4096);
     if (rounds < 1) rounds = 1;
     if (rounds > 4) rounds = 4;
-    if (rounds_env > 0) rounds = rounds_env;
     int64_t want = rounds * 256 / tiles;
     if (want < 1) want = 1;
     const int64_t min_stages = x3 == 6 ? 2 : 16;      // >= 16 (X3: 12) steps per split
@@ -449,14 +445,12 @@ void umr_tn256_plan(const umr_gemm_tn_desc* d, int* splits, int* rows_per_split)
 int umr_launch_gemm_tn256(const umr_gemm_tn_desc* d, int splits, int rows_per_split, float* slab, float* bslab, hipStream_t s) {
     const int tiles_n = (d->N + 255) / 256, tiles_k = (d->K + 255) / 256;
     dim3 g((unsigned)(tiles_n * tiles_k * splits)), b(512);
-    static const int mapmode = umr_env_int("UMR_TN_MAP", 3);
-    static const int ph2 = umr_env_int("UMR_TN256_PH2", 1);   // two-phase stage: +1-2 % (tools/kbench.py)
+    constexpr int mapmode = 3;   // column mapping of both operands (see the kernel's staging and epilogue)
+    // plain and conv weight gradients in the two-phase stage form (+1-2 % over the single-phase one, tools/kbench.py)
 #define LT(CV, WFV)                                                                                                    \
     do {                                                                                                               \
-        UMR_SET_MAX_LDS_ONCE((gemm_tn256_kernel<CV, false, WFV>), TLDS); \
-        UMR_SET_MAX_LDS_ONCE((gemm_tn256_kernel<CV, true, WFV>), TLDS);                                                                                                              \
-        if (ph2) hipLaunchKernelGGL((gemm_tn256_kernel<CV, true, WFV>), g, b, TLDS, s, *d, tiles_k, tiles_n * tiles_k, rows_per_split, slab, bslab, mapmode, 1); \
-        else hipLaunchKernelGGL((gemm_tn256_kernel<CV, false, WFV>), g, b, TLDS, s, *d, tiles_k, tiles_n * tiles_k, rows_per_split, slab, bslab, mapmode, 1);   \
+        UMR_SET_MAX_LDS_ONCE((gemm_tn256_kernel<CV, true, WFV>), TLDS);                                                \
+        hipLaunchKernelGGL((gemm_tn256_kernel<CV, true, WFV>), g, b, TLDS, s, *d, tiles_k, tiles_n * tiles_k, rows_per_split, slab, bslab, mapmode, 1); \
     } while (0)
 #define LTX(CV, WFV)                                                                                                   \
     do {                                                                                                               \

@@ -51,12 +51,8 @@ __global__ __launch_bounds__(256) void lh_fwd_kernel(const T* __restrict__ x, co
 // coalesced 512-byte (bf16) access and every element of the big tensor is touched once (the first version walked the 9
 // taps per output pixel and pulled every channel vector nine times through L1/L2: 10.6 + 6.6 ms at cfg2, against the
 // 1.2 + 2.4 ms of the HBM traffic).
-#ifndef LH_WEIGHT_UNROLL
-#define LH_WEIGHT_UNROLL 4
-#endif
-#ifndef LH_DATA_UNROLL
-#define LH_DATA_UNROLL 1
-#endif
+constexpr int LH_WEIGHT_UNROLL = 4;
+constexpr int LH_DATA_UNROLL = 1;
 struct RunG { float g[3][3]; };   // [row dy = -1,0,1][column shift dx = -1,0,1], lane l <-> pixel x0 + l
 
 __device__ __forceinline__ RunG load_run_g(const float* __restrict__ dout, const float* __restrict__ yout, int64_t rowbase, int py, int x0,
@@ -344,9 +340,7 @@ __global__ __launch_bounds__(256) void small_gemm_wave_kernel(const float* __res
     }
 }
 
-#ifndef LH_BLOCKS_CAP
-#define LH_BLOCKS_CAP 2048
-#endif
+constexpr int LH_BLOCKS_CAP = 2048;
 int lh_blocks(int64_t M) { int64_t nb = (M + 4095) / 4096; if (nb > LH_BLOCKS_CAP) nb = LH_BLOCKS_CAP; if (nb < 1) nb = 1; return (int)nb; }   // upper bound on partial slabs (8 blocks per CU)
 
 }  // namespace

@@ -211,9 +211,7 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const T* __restrict__ dy, c
 }
 
 // bf16 fast path of the backward (see ln_fwd_bf16x8_kernel): 16-byte loads, two rows per wave and iteration
-#ifndef LN_BWD_ROWS
-#define LN_BWD_ROWS 1   // rows per wave and iteration: 1 measured 6 % faster than 2 at 36928 x 768 (fewer registers), 4 is 60 % slower
-#endif
+constexpr int LN_BWD_ROWS = 1;   // rows per wave and iteration: 1 measured 6 % faster than 2 at 36928 x 768 (fewer registers), 4 is 60 % slower
 template <int NCH, int R = LN_BWD_ROWS>
 __global__ __launch_bounds__(256) void ln_bwd_bf16x8_kernel(const bf16_t* __restrict__ dy, const bf16_t* __restrict__ x,
                                                             const float* __restrict__ gamma, const float* __restrict__ mean,
@@ -393,8 +391,7 @@ static void ln_bwd_plan(int M, int* nb_out, int* rpb_out) {
             return (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
                        ? prop.multiProcessorCount : 256;
         }();
-        // UMR_LN_BWD_WG_PER_CU: experiment hook (register use decides how many are co-resident); initialised once, thread-safe
-        static const int wg_per_cu = [] { const char* e = getenv("UMR_LN_BWD_WG_PER_CU"); const int v = e ? atoi(e) : 2; return v < 1 ? 2 : v; }();
+        constexpr int wg_per_cu = 2;
         if (nb > wg_per_cu * cus) nb = wg_per_cu * cus;
     }
     const int rpb = (M + nb - 1) / nb;

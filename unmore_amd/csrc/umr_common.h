@@ -111,10 +111,6 @@ static __device__ uint4 umr_zero_page[16];
         }                                                                                                           \
     } while (0)
 
-// environment switch read ONCE per process, thread-safely:  static const int v = umr_env_int("NAME", dflt);
-#include <stdlib.h>
-static inline int umr_env_int(const char* name, int dflt) { const char* e = getenv(name); return e ? atoi(e) : dflt; }
-
 // Debug / A-B options that can change WHILE the process runs (tests and probes switch them between launches): include/umr.h,
 // umr_set_debug_option.  Each is read from the environment once, when the library is loaded; on the launch path an option costs one
 // relaxed atomic load -- no getenv per launch (round-5 review: getenv is not thread-safe against setenv and made the library's

@@ -327,25 +327,16 @@ def _rep_bias(b, reps):
     return ops.permute4(b.detach(), out, (1, 1, reps, b.numel()), (0, 0, 0, 1))
 
 
-_FUSE_HEAD_OUT = os.environ.get("UMR_FUSE_HEAD_OUT", "1") != "0"  # A/B switch for benchmarking
-_X3_HEADS = os.environ.get("UMR_X3_HEADS", "1") != "0"            # A/B switch: fp32-mode inference heads on the bf16-plane kernel
-_X3_ALL = os.environ.get("UMR_X3_ALL", "1") != "0"            # A/B switch: 0 = fp32 mode as in round 3 (only the heads on the plane kernels)
-_MERGE_DFEAT = os.environ.get("UMR_MERGE_DFEAT", "1") != "0"    # A/B switch: one GEMM for the feature-map gradient of both heads
+_FUSE_HEAD_OUT = True   # the heads' 1024 -> {1,2} output layer in the epilogue of the GEMM before it (tests switch it off)
 # A 1x1 convolution and a bilinear resize commute exactly (both linear, one per pixel across channels, the other per channel across
 # pixels with weights that sum to 1, so the bias commutes too): conv1x1(resize(x)) == resize(conv1x1(x)).  The fusion blocks'
 # out_conv (blocks.py:377-381: interpolate x2, then out_conv) and the first layer of both heads (objectness_net.py:110,121 on the
 # x2-interpolated feature map, models.py:70-72) therefore run on the map BEFORE the resize -- a quarter of the rows in the GEMM, its
-# weight gradient and its data gradient -- and the resize moves the GEMM's output.  0 = the reference's order (A/B switch).
-_COMMUTE_RESIZE = os.environ.get("UMR_COMMUTE_RESIZE", "1") != "0"
-# Backward of a head without non-linearities between its convs (objectness_net.py:119-142): "algebraic" (default) = exact
-# gradients of all eight factored tensors from three pixel reductions (no 512/1024-channel tensor is stored, read or
-# multiplied in backward); "gemm" = the layer-by-layer data/weight-gradient GEMMs (A/B switch, the round-1 form).
-_LINEAR_HEAD_BWD = os.environ.get("UMR_LINEAR_HEAD_BWD", "algebraic")
+# weight gradient and its data gradient -- and the resize moves the GEMM's output.  False = the reference's order (tests).
+_COMMUTE_RESIZE = True
 
 
 _WGRAD_STREAM = os.environ.get("UMR_WGRAD_STREAM", "auto")   # weight gradients on a second stream: auto (small problems) | 0 | 1
-# LayerNorm's parameter gradients (the reduction pass of layernorm_bwd) ride on the weight-gradient lane when there is one (A/B switch)
-_LN_PARAMS_SIDE = os.environ.get("UMR_LN_PARAMS_SIDE", "1") != "0"
 _side_streams = {}
 
 
@@ -406,7 +397,10 @@ class WgradStream:
 class Engine(X3Path):
     def __init__(self, cfg, head_layouts, compute_dtype=torch.float32, collapse_linear_heads=False, linear_head_backward=None):
         self.cfg = cfg
-        self.linear_head_backward = linear_head_backward or _LINEAR_HEAD_BWD
+        # backward of a head without non-linearities between its convs (objectness_net.py:119-142): "algebraic" = exact gradients of
+        # all eight factored tensors from three pixel reductions (no 512/1024-channel tensor is stored, read or multiplied in
+        # backward); "gemm" = the layer-by-layer data/weight-gradient GEMMs (the round-1 form)
+        self.linear_head_backward = linear_head_backward or "algebraic"
         assert self.linear_head_backward in ("algebraic", "gemm")
         self.center_layout, self.sdf_layout = head_layouts
         self.dt = compute_dtype
@@ -605,7 +599,7 @@ class Engine(X3Path):
         object_reasoning.py:379-487 read the boundary-distance map alone, and the centre head is most of a 128x128 crop's forward."""
         cfg, dt = self.cfg, self.dt
         assert not (skip and save), "skip: inference only"
-        if _X3_ALL and dt == torch.float32 and ops.get_f32_mode() in ("x3", "x3_fast"):
+        if dt == torch.float32 and ops.get_f32_mode() in ("x3", "x3_fast"):
             return self.forward_x3(P, images, save, skip)      # fp32 parity mode on the bf16-plane kernels (engine_x3.py)
         assert images.is_cuda and images.dtype == torch.float32 and images.dim() == 4 and images.shape[1] == 3
         images = images.contiguous()
@@ -760,11 +754,10 @@ class Engine(X3Path):
             H, W = 2 * path.shape[1], 2 * path.shape[2]
             if save:
                 S["H"], S["W"] = H, W
-        x3_ok = _X3_HEADS and dt == torch.float32 and ops.get_f32_mode() in ("x3", "x3_fast")
         # the heads' first layer before the final resize (_COMMUTE_RESIZE): the interpolated 256-channel feature map is never
         # formed, and the backward of that layer -- weight gradient, data gradient, the algebraic head's reductions -- runs on
         # the quarter-size map
-        lowres = _COMMUTE_RESIZE and not x3_ok
+        lowres = _COMMUTE_RESIZE
         feat = ops.bilinear_fwd(path, H, W, True) if not lowres else None
         if save:
             S["fus"] = fus_saved
@@ -777,23 +770,12 @@ class Engine(X3Path):
         # ---- heads (objectness_net.py:109-135)
         outs = []
         heads_saved = []
-        # fp32 (parity) mode at inference: the heads' three big layers run on the persistent 256x256 bf16 kernel with every f32
-        # value held as three bf16 planes (six plane pairs per K-tile, csrc/gemm_nt256p.hip X3) -- the same six-term products as
-        # the 128x128 fp32 kernel's in-register split (UMR_F32_X3), without the split arithmetic in the loop.  Training keeps
-        # f32 activations (its backward reads them), and the exact-f32 mode keeps the f32 MFMA.
-        featp = None
         for name, lay in (("center_field_prediction_head", self.center_layout), ("sdf_prediction_head", self.sdf_layout)):
             if name in skip:
                 outs.append(None)
                 continue
             idx = lay["conv_idx"]
-            # in training the plane form serves the heads that keep no activation for their backward (algebraic backward)
-            alg_ = save and not lay["relu"] and lay["final"] != "sine" and self.linear_head_backward == "algebraic"
-            collapse = self._collapse(lay, save)
-            x3_heads = x3_ok and (not save or alg_) and not collapse
-            if x3_heads and featp is None:
-                featp = ops.split3(feat.view(-1, 256))
-            if collapse:
+            if self._collapse(lay, save):
                 if lowres:
                     out, cs = self._linear_head_forward_lowres(P, name, idx, path, H, W, _ACT[lay["final"]], save)
                 else:
@@ -804,41 +786,10 @@ class Engine(X3Path):
                     heads_saved.append(cs)
                 continue
             act = L.ACT_RELU if lay["relu"] else L.ACT_NONE
-            if x3_heads:
-                b_ = lambda k: self._f32(P, f"{name}.{idx[k]}.bias")
-                h1p = ops.gemm_nt_x3(featp, self._wx3(P, f"{name}.{idx[0]}.weight", "lin"), b_(0), act=act, out_planes=True)
-                h2p = ops.gemm_nt_x3(h1p.view(B, H, W, -1), self._wx3(P, f"{name}.{idx[1]}.weight", "c3"), b_(1), act=act, conv=1, out_planes=True)
-                del h1p
-                # the 1024 -> {1,2} output layer rides in the epilogue of the layer that produces its input: h3 is never stored
-                w4 = self._f32(P, f"{name}.{idx[3]}.weight")
-                parts = ops.gemm_nt_x3(h2p, self._wx3(P, f"{name}.{idx[2]}.weight", "lin"), b_(2), act=act,
-                                       red_w=w4.reshape(w4.shape[0], -1).contiguous())
-                del h2p
-                out = ops.head_out_finish(parts, b_(3), B, H, W, _ACT[lay["final"]])
-                del parts
-                outs.append(out)
-                if save:
-                    heads_saved.append(dict(algebraic=True, act=_ACT[lay["final"]], out=out))
-                continue
             # a head that is linear up to its output activation needs none of its 512/1024-channel activations in backward
             # (exact gradients from three pixel reductions over feat, _linear_head_backward); sin is not invertible from its value
             algebraic = save and not lay["relu"] and lay["final"] != "sine" and self.linear_head_backward == "algebraic"
             keep = save and not algebraic
-            if x3_ok and keep and lay["final"] != "sine":
-                # fp32 training, a head whose backward reads its activations: the three big layers on the plane kernel with f32
-                # outputs (saved for the backward as before), a split pass between them
-                if featp is None:
-                    featp = ops.split3(feat.view(-1, 256))
-                b_ = lambda k: self._f32(P, f"{name}.{idx[k]}.bias")
-                h1 = ops.gemm_nt_x3(featp, self._wx3(P, f"{name}.{idx[0]}.weight", "lin"), b_(0), act=act)
-                h2 = ops.gemm_nt_x3(ops.split3(h1).view(B, H, W, -1), self._wx3(P, f"{name}.{idx[1]}.weight", "c3"), b_(1), act=act, conv=1)
-                h3 = ops.gemm_nt_x3(ops.split3(h2), self._wx3(P, f"{name}.{idx[2]}.weight", "lin"), b_(2), act=act)
-                w4 = self._f32(P, f"{name}.{idx[3]}.weight")
-                out = ops.head_out_fwd(h3, w4.reshape(w4.shape[0], -1), b_(3), B, H, W, _ACT[lay["final"]])
-                outs.append(out)
-                heads_saved.append(dict(h1=h1, h2=h2, h3=h3, out=out, x3=True))
-                del h1, h2, h3
-                continue
             if lowres:
                 h1l = ops.gemm_nt(path.view(-1, 256), self._w(P, f"{name}.{idx[0]}.weight", "lin"), self._f32(P, f"{name}.{idx[0]}.bias"))
                 h1 = ops.bilinear_fwd(h1l.view(path.shape[0], path.shape[1], path.shape[2], -1), H, W, True, relu=lay["relu"]).view(B * H * W, -1)
@@ -884,7 +835,7 @@ class Engine(X3Path):
         # Both heads factored: their layer-1 input gradients dh1 go side by side into one [M, 2*C1] buffer and the gradient of
         # the shared feature map is ONE GEMM over K = 2*C1 (instead of a GEMM plus a second one that re-reads and re-writes
         # the [M, 256] result to accumulate into it).
-        merge_dfeat = _MERGE_DFEAT and all(not (hs_.get("collapsed") or hs_.get("algebraic")) for hs_ in S["heads"])
+        merge_dfeat = all(not (hs_.get("collapsed") or hs_.get("algebraic")) for hs_ in S["heads"])
         dh1cat, w1cat = None, []
         for hi, (name, lay, dout) in enumerate((("center_field_prediction_head", self.center_layout, d_center),
                                                ("sdf_prediction_head", self.sdf_layout, d_sdf))):
@@ -899,11 +850,7 @@ class Engine(X3Path):
                                    G[f"{name}.{idx[3]}.weight"].view(w4.shape[0], -1), G[f"{name}.{idx[3]}.bias"])
             hs["h3"] = None
             wgrad_lin(f"{name}.{idx[2]}.weight", dh3, hs["h2"], f"{name}.{idx[2]}.bias")
-            x3b = bool(hs.get("x3")) and dt == torch.float32
-            if x3b:
-                dh2 = ops.gemm_nt_x3(ops.split3(dh3), self._wx3(P, f"{name}.{idx[2]}.weight", "lin_t"), None, mask=(hs["h2"] if relu else None))
-            else:
-                dh2 = ops.gemm_nt(dh3, self._w(P, f"{name}.{idx[2]}.weight", "lin_t"), None, aux=(hs["h2"] if relu else None), mask_relu=relu)
+            dh2 = ops.gemm_nt(dh3, self._w(P, f"{name}.{idx[2]}.weight", "lin_t"), None, aux=(hs["h2"] if relu else None), mask_relu=relu)
             del dh3
             h1 = hs["h1"].view(B, H, W, 512)
             wgrad_c3(f"{name}.{idx[1]}.weight", dh2, h1, f"{name}.{idx[1]}.bias")
@@ -911,13 +858,9 @@ class Engine(X3Path):
             c1 = hs["h1"].shape[-1]
             if merge_dfeat and dh1cat is None:
                 dh1cat = torch.empty((B * H * W, 2 * c1), dtype=dt, device=dev)
-            if x3b and not merge_dfeat:
-                dh1 = ops.gemm_nt_x3(ops.split3(dh2).view(B, H, W, -1), self._wx3(P, f"{name}.{idx[1]}.weight", "c3_d"), None, conv=1,
-                                     mask=(hs["h1"] if relu else None))
-            else:
-                dh1 = ops.gemm_nt(dh2.view(B, H, W, 512), self._w(P, f"{name}.{idx[1]}.weight", "c3_d"), None, conv=1,
-                                  aux=(hs["h1"] if relu else None), mask_relu=relu,
-                                  out=(dh1cat[:, hi * c1:(hi + 1) * c1] if merge_dfeat else None))
+            dh1 = ops.gemm_nt(dh2.view(B, H, W, 512), self._w(P, f"{name}.{idx[1]}.weight", "c3_d"), None, conv=1,
+                              aux=(hs["h1"] if relu else None), mask_relu=relu,
+                              out=(dh1cat[:, hi * c1:(hi + 1) * c1] if merge_dfeat else None))
             del dh2
             hs["h1"] = None
             wgrad_lin(f"{name}.{idx[0]}.weight", dh1, feat.view(-1, 256), f"{name}.{idx[0]}.bias")
@@ -1014,7 +957,7 @@ class Engine(X3Path):
         # LayerNorm's dgamma / dbeta are weight gradients too: in a chain-of-graphs step their reduction pass leaves the data-gradient chain
         # for the weight-gradient lane (48 launches of the reference recipe's step; +0.7 %).  Not in the eager two-stream schedule, whose
         # host is the slower side in backward: a hand-over costs it more than the 4-us kernel costs the GPU.
-        ln_via = wg.run if (wg.staged is not None and _LN_PARAMS_SIDE) else None
+        ln_via = wg.run if wg.staged is not None else None
 
         def cb(name):
             if join_at_stages:

@@ -377,7 +377,7 @@ class X3Path:
 
     # ------------------------------------------------------------------ backward
     def backward_x3(self, P, S, d_center, d_sdf, G, stage_cb=None, join_at_stages=False):
-        from .engine import _ACT, _LN_PARAMS_SIDE, _unpack_conv3_grad, WgradStream
+        from .engine import _ACT, _unpack_conv3_grad, WgradStream
         cfg = self.cfg
         B, H, W, gh, gw = S["B"], S["H"], S["W"], S["gh"], S["gw"]
         D, heads, p = cfg["D"], cfg["heads"], cfg["patch"]
@@ -387,7 +387,7 @@ class X3Path:
         # LayerNorm's dgamma / dbeta are weight gradients too: in a chain-of-graphs step their reduction pass leaves the data-gradient chain
         # for the weight-gradient lane (48 launches of the reference recipe's step; +0.7 %).  Not in the eager two-stream schedule, whose
         # host is the slower side in backward: a hand-over costs it more than the 4-us kernel costs the GPU.
-        ln_via = wg.run if (wg.staged is not None and _LN_PARAMS_SIDE) else None
+        ln_via = wg.run if wg.staged is not None else None
         mm = lambda *a, **k: self._mm(P, *a, **k)
 
         def cb(name):

@@ -16,11 +16,11 @@ import os
 from . import graphs, ops
 from .parallel import BucketedAllReduce
 
-_BATCHED_REPACK = os.environ.get("UMR_BATCHED_REPACK", "1") != "0"   # A/B switch: 0 = drop the packed copies, re-pack lazily (round 2)
-# A/B switch: 0 = per stage, the Adam launch and then the batched refresh of its packed copies (round 5); 1 = the Adam launch writes the
-# bf16 copies of the stage's Linear weights itself (round 6: ops.adam_pack; bit-identical)
+_BATCHED_REPACK = True   # False = drop the packed copies, re-pack lazily (round 2; tests compare the two)
+# True = the Adam launch writes the bf16 copies of the stage's Linear weights itself (round 6: ops.adam_pack; bit-identical); False = per
+# stage, the Adam launch and then the batched refresh of its packed copies (round 5; tests compare the two)
+_ADAM_PACK = True
 _DP_ADAM_LAG = max(1, int(os.environ.get("UMR_DP_ADAM_LAG", "2")))   # stages between a bucket's all-reduce and its optimizer update
-_ADAM_PACK = os.environ.get("UMR_ADAM_PACK", "1") != "0"
 
 
 def _stage_of(name, cfg):
