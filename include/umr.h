@@ -418,6 +418,53 @@ int umr_maxpool3x3s2(const void* x, void* y, int B, int H, int W, int C, int dty
 int umr_bn_fold(const float* w, const float* gamma, const float* beta, const float* mean, const float* var, float eps, void* w_out,
                 float* b_out, int Co, int K, int ldk, int dtype, umr_stream_t stream);
 
+/* ---- existence-classifier training (train_objectness_net.py:540-743, BinaryClassifierTrainer; csrc/clf_train.hip) ----
+ * Layout NHWC: a map is [M rows][C channels] with M = B*H*W; storage f32 or bf16 (dtype), statistics and sums in f32.  Every
+ * reduction is deterministic: fixed row chunks per (M, C), per-chunk partials combined in a fixed order, no float atomics.
+ * bn_train_stats: training-mode BatchNorm2d statistics of a raw conv output z: mean, rstd = 1/sqrt(var_biased + eps) (f32 [C]),
+ *   from shifted sums (shift = row 0 of each channel; no E[x^2]-E[x]^2 cancellation).  Non-null running_mean / running_var are
+ *   updated as nn.BatchNorm2d does (r = (1-momentum) r + momentum s, with the unbiased variance; M > 1), and a non-null
+ *   num_batches_tracked is incremented by one.  workspace >= umr_bn_train_workspace(M, C).
+ * bn_train_apply: y = act(gamma (z - mean) rstd + beta [+ gamma2 (z2 - mean2) rstd2 + beta2 | + residual]); act: 0 none, 1 ReLU.
+ * bn_train_bwd_reduce / _apply (one umr_bn_bwd_desc for both): g = dy, or dpool[row / rows_per_batch] * pool_scale (the avg-pool
+ *   backward, broadcast here), zeroed where the saved post-activation y <= 0 when y is given.  For each of nbranch (1 or 2) BNs
+ *   that fed the same sum: _reduce writes dbeta = sum g and dgamma = sum g * xhat (xhat recomputed from z, mean, rstd);
+ *   _apply reads them back and writes dz = gamma rstd (g - dbeta/M - xhat dgamma/M), and g itself to g_out when non-null.
+ * maxpool3x3s2_bwd: gradient of umr_maxpool3x3s2 in gather form: each input pixel sums the gradients of the (<= 4) windows
+ *   whose first maximum in (ky, kx) scan order it is, recomputed from the saved pool input x.
+ * stuff2_add: dst[b][2y][2x][c] += src[b][y][x][c] (the data gradient of a stride-2 1x1 convolution scattered into the map).
+ * bce_sigmoid: loss[0] = mean_i BCE(sigmoid(logit_i), label_i) with torch's clamps (log >= -100; the backward divides by
+ *   max(p (1-p), 1e-12)), dlogit[i] = d loss / d logit_i; one launch. */
+typedef struct umr_bn_bwd_desc {
+    const void* dy;              /* [M, C] or NULL (then dpool) */
+    const float* dpool;          /* [M / rows_per_batch, C] f32 */
+    const void* y;               /* optional [M, C]: ReLU mask source */
+    const void* z[2];            /* [M, C] raw conv outputs */
+    const float* mean[2];
+    const float* rstd[2];
+    const float* gamma[2];
+    float* dgamma[2];
+    float* dbeta[2];
+    void* dz[2];                 /* [M, C] (_apply) */
+    void* g_out;                 /* optional [M, C] (_apply) */
+    void* workspace;             /* >= umr_bn_train_workspace(M, C) bytes (_reduce) */
+    int64_t workspace_bytes;
+    int64_t rows_per_batch;
+    float pool_scale;
+    int32_t M, C, nbranch, dtype;
+} umr_bn_bwd_desc;
+int64_t umr_bn_train_workspace(int M, int C);
+int umr_bn_train_stats(const void* z, float* mean, float* rstd, float* running_mean, float* running_var, int64_t* num_batches_tracked,
+                       void* workspace, int64_t workspace_bytes, int M, int C, float eps, float momentum, int dtype, umr_stream_t stream);
+int umr_bn_train_apply(const void* z, const float* mean, const float* rstd, const float* gamma, const float* beta, const void* z2,
+                       const float* mean2, const float* rstd2, const float* gamma2, const float* beta2, const void* residual, void* y,
+                       int M, int C, int act, int dtype, umr_stream_t stream);
+int umr_bn_train_bwd_reduce(const umr_bn_bwd_desc* d, umr_stream_t stream);
+int umr_bn_train_bwd_apply(const umr_bn_bwd_desc* d, umr_stream_t stream);
+int umr_maxpool3x3s2_bwd(const void* dy, const void* x, void* dx, int B, int H, int W, int C, int dtype, umr_stream_t stream);
+int umr_stuff2_add(const void* src, void* dst, int B, int H, int W, int C, int dtype, umr_stream_t stream);
+int umr_bce_sigmoid(const float* logit, const float* label, float* loss, float* dlogit, int B, umr_stream_t stream);
+
 /* ---- ground-truth synthesis on the device (datasets.py:158-159,171-222 without random crop) -------
  * mask [B,H,W] u8 (non-zero = object) at the training resolution; center_xy [B,2] f32 (x, y) object centres in the same
  * pixel coordinates, or NULL = bounding-box centre of each mask ((min+max)/2, datasets.py:158-159).

@@ -44,6 +44,12 @@ class AdamPackEntry(ctypes.Structure):   # umr_adam_pack_entry
                 ("blk_start", _i64)]
 
 
+class BnBwdDesc(ctypes.Structure):   # umr_bn_bwd_desc
+    _fields_ = [("dy", _vp), ("dpool", _vp), ("y", _vp), ("z", _vp * 2), ("mean", _vp * 2), ("rstd", _vp * 2), ("gamma", _vp * 2),
+                ("dgamma", _vp * 2), ("dbeta", _vp * 2), ("dz", _vp * 2), ("g_out", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
+                ("rows_per_batch", _i64), ("pool_scale", ctypes.c_float), ("M", _i32), ("C", _i32), ("nbranch", _i32), ("dtype", _i32)]
+
+
 class PermEntry(ctypes.Structure):   # umr_perm_entry
     _fields_ = [("src", _vp), ("dst", _vp), ("d", _i32 * 4), ("sstride", _i64 * 4), ("soff", _i64), ("dtype_in", _i32), ("dtype_out", _i32),
                 ("blk_start", _i64), ("e", _i32 * 4), ("ord", _i32 * 4), ("rowlen", _i64)]
@@ -80,6 +86,14 @@ _SIGS = {
     "umr_im2col_nchw": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "umr_maxpool3x3s2": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "umr_bn_fold": [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
+    "umr_bn_train_workspace": [_i32, _i32],
+    "umr_bn_train_stats": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _f32, _i32, _vp],
+    "umr_bn_train_apply": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
+    "umr_bn_train_bwd_reduce": [_vp, _vp],
+    "umr_bn_train_bwd_apply": [_vp, _vp],
+    "umr_maxpool3x3s2_bwd": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
+    "umr_stuff2_add": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
+    "umr_bce_sigmoid": [_vp, _vp, _vp, _vp, _i32, _vp],
     "umr_head_out_finish": [_vp, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp],
     "umr_gemm_tn": [_vp, _vp],
     "umr_gemm_tn_workspace": [_vp],
@@ -167,7 +181,8 @@ def lib():
         _set_argtypes(_lib)
         for fn in ("umr_gemm_tn_workspace", "umr_layernorm_bwd_workspace", "umr_head_out_bwd_workspace", "umr_loss_workspace",
                    "umr_linear_head_bwd_weight_workspace", "umr_linear_head_shift9_workspace", "umr_label_synthesis_workspace", "umr_attention_bwd_workspace",
-                   "umr_distance_transform_workspace", "umr_gemm_nt_workspace", "umr_gemm_nt_x3_workspace", "umr_nms_workspace"):
+                   "umr_distance_transform_workspace", "umr_gemm_nt_workspace", "umr_gemm_nt_x3_workspace", "umr_nms_workspace",
+                   "umr_bn_train_workspace"):
             getattr(_lib, fn).restype = ctypes.c_int64
     return _lib
 

@@ -6,10 +6,12 @@ reference builds it, with the same constructor, the same 322-key `state_dict()` 
 probabilities, so `object_reasoning.py:64-90,491-523` / `object_scoring.py:65-90,123-140` can construct it,
 `load_state_dict(strict=True)` a released checkpoint and call it unchanged.
 
-Only the path those callers use is implemented: eval mode (BatchNorm with running statistics, folded into the convs), no
+`forward` implements the path those callers use: eval mode (BatchNorm with running statistics, folded into the convs), no
 gradients.  The sub-modules only HOLD parameters and buffers; the arithmetic runs on the HIP kernels (umr_gemm_nt for all
 53 convolutions and both Linear layers, csrc/classifier.hip for the stem im2col / max-pool / BN folding).  There is no CPU
-path and no training path: both raise.
+path, and `forward` refuses training mode: to train the classifier (train_objectness_net.py:540-743) use
+`unmore_amd.ClassifierTrainStep(model)`, which runs its own schedule over these parameters and buffers
+(unmore_amd/classifier_trainer.py).
 """
 import torch
 from torch import nn

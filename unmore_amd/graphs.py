@@ -330,3 +330,31 @@ from ._lib import _count as _launches     # libumr launches so far (counted by _
 
 
 CAPTURE_TYPES = (Captured, StagedCaptured)
+
+
+def replay_or_capture(table, key, ins, make_capture):
+    """The capture policy of the train steps (trainer.TrainStep, classifier_trainer.ClassifierTrainStep).  `table` maps a call key to
+    its eager-call count, then to its capture.  The first WARMUP_CALLS calls of a key run eagerly: they pack every weight, build the
+    batched refresh and size the workspaces.  The next call captures (make_capture(): a Captured / StagedCaptured of the step body on
+    `ins`) and replays the capture, which only RECORDED the step.  A capture that went stale (valid() false: the packed weights moved,
+    a state dict was reloaded) is warmed up and captured again; one that failed stays eager.  Every capture keeps its own pools of
+    temporaries: a loop whose batch size keeps changing (the reference's batch filter, train_objectness_net.py:190-207) holds at most
+    MAX_CAPTURES of them.  Returns the replay's outputs, or None when this call is to run eagerly."""
+    ent = table.get(key)
+    if isinstance(ent, CAPTURE_TYPES):
+        if ent.valid():
+            return ent.replay(*ins)
+        if ent.failed is not None:
+            return None
+        ent = None
+    n = (ent or 0) + 1
+    table[key] = n
+    if n <= WARMUP_CALLS:
+        return None
+    if sum(isinstance(v, CAPTURE_TYPES) for v in table.values()) >= MAX_CAPTURES:
+        for k in [k for k, v in table.items() if isinstance(v, CAPTURE_TYPES)]:
+            del table[k]
+        release_dropped()
+    cap = make_capture()
+    table[key] = cap
+    return cap.replay(*ins) if cap.failed is None else None

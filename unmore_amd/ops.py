@@ -945,13 +945,127 @@ def maxpool3x3s2(x):
     return y
 
 
-def bn_fold(w2d, gamma, beta, mean, var, eps, ldk, dtype):
-    """Fold eval-mode BatchNorm into packed conv weight rows w2d [Co,K] f32 -> ([Co,ldk] dtype, bias [Co] f32)."""
+def bn_fold(w2d, gamma, beta, mean, var, eps, ldk, dtype, w_out=None, b_out=None):
+    """Fold eval-mode BatchNorm into packed conv weight rows w2d [Co,K] f32 -> ([Co,ldk] dtype, bias [Co] f32); w_out / b_out: write
+    into these instead of new tensors."""
     _need_gpu(w2d)
     assert w2d.dtype == torch.float32 and w2d.is_contiguous() and all(t.dtype == torch.float32 for t in (gamma, beta, mean, var))
     Co, K = w2d.shape
-    w_out = torch.empty((Co, ldk), dtype=dtype, device=w2d.device)
-    b_out = torch.empty((Co,), dtype=torch.float32, device=w2d.device)
+    if w_out is None:
+        w_out = torch.empty((Co, ldk), dtype=dtype, device=w2d.device)
+    if b_out is None:
+        b_out = torch.empty((Co,), dtype=torch.float32, device=w2d.device)
+    assert w_out.shape == (Co, ldk) and w_out.dtype == dtype and w_out.is_contiguous() and b_out.numel() == Co
     L.check(L.lib().umr_bn_fold(_p(w2d), _p(gamma), _p(beta), _p(mean), _p(var), eps, _p(w_out), _p(b_out), Co, K, ldk, _DT[dtype], _stream()),
             "umr_bn_fold")
     return w_out, b_out
+
+
+# ---- existence-classifier training pieces (csrc/clf_train.hip)
+def _rows(t):
+    """(M, C) of an NHWC map / [M, C] matrix with contiguous storage"""
+    assert t.is_contiguous()
+    return t.numel() // t.shape[-1], t.shape[-1]
+
+
+def bn_train_stats(z, running_mean=None, running_var=None, num_batches_tracked=None, eps=1e-5, momentum=0.1):
+    """Batch statistics of a raw conv output z ([..., C], f32 or bf16) -> (mean, rstd) f32 [C]; updates the running statistics and
+    the batch counter in place when given (nn.BatchNorm2d in training mode)."""
+    _need_gpu(z, running_mean, running_var, num_batches_tracked)
+    M, C = _rows(z)
+    for t in (running_mean, running_var):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == C), f"bn_train_stats: running statistics f32 [{C}]"
+    assert num_batches_tracked is None or (num_batches_tracked.dtype == torch.int64 and num_batches_tracked.numel() == 1)
+    mean = torch.empty(C, dtype=torch.float32, device=z.device)
+    rstd = torch.empty(C, dtype=torch.float32, device=z.device)
+    ws = _workspace(L.lib().umr_bn_train_workspace(M, C), z.device)
+    L.check(L.lib().umr_bn_train_stats(_p(z), _p(mean), _p(rstd), _p(running_mean), _p(running_var), _p(num_batches_tracked), _p(ws), ws.numel(),
+                                       M, C, eps, momentum, _DT[z.dtype], _stream()), "umr_bn_train_stats")
+    return mean, rstd
+
+
+def bn_train_apply(z, mean, rstd, gamma, beta, relu=True, second=None, residual=None, out=None):
+    """y = act(gamma (z - mean) rstd + beta [+ second BN (z2, mean2, rstd2, gamma2, beta2) | + residual]), same shape / dtype as z"""
+    _need_gpu(z)
+    M, C = _rows(z)
+    z2, m2, r2, g2, b2 = second if second is not None else (None,) * 5
+    _need_gpu(mean, rstd, gamma, beta, z2, m2, r2, g2, b2, residual)
+    for t in (z2, residual):
+        assert t is None or (t.shape == z.shape and t.dtype == z.dtype and t.is_contiguous())
+    for t in (mean, rstd, gamma, beta, m2, r2, g2, b2):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == C), f"bn_train_apply: per-channel operands f32 [{C}]"
+    y = torch.empty_like(z) if out is None else out
+    L.check(L.lib().umr_bn_train_apply(_p(z), _p(mean), _p(rstd), _p(gamma), _p(beta), _p(z2), _p(m2), _p(r2), _p(g2), _p(b2), _p(residual),
+                                       _p(y), M, C, int(relu), _DT[z.dtype], _stream()), "umr_bn_train_apply")
+    return y
+
+
+def bn_train_bwd(branches, dy=None, dpool=None, rows_per_batch=0, pool_scale=1.0, y=None, want_g=False):
+    """Backward of one or two training-mode BatchNorms whose outputs were summed (then ReLU'd when `y`, the saved post-activation, is
+    given).  branches: [(z, mean, rstd, gamma, dgamma_out, dbeta_out)]; the gradient of the sum is dy, or dpool [B, C] f32 broadcast
+    over rows_per_batch rows and scaled by pool_scale (the avg-pool backward).  Writes dgamma / dbeta; returns [dz per branch]
+    (+ the masked gradient itself with want_g: the identity shortcut's share)."""
+    z0 = branches[0][0]
+    _need_gpu(z0, dy, dpool, y)
+    M, C = _rows(z0)
+    assert 1 <= len(branches) <= 2 and z0.dtype in _DT
+    assert (dy is None) != (dpool is None), "one gradient source: dy or dpool"
+    for t in (dy, y):     # maps of z's layout and storage type (the kernels read them as z's dtype)
+        assert t is None or (t.dtype == z0.dtype and t.is_contiguous() and t.numel() == M * C and t.shape[-1] == C), \
+            f"bn_train_bwd: dy / y must be contiguous [{M}, {C}] {z0.dtype}"
+    if dpool is not None:
+        assert rows_per_batch > 0 and M % rows_per_batch == 0
+        assert dpool.dtype == torch.float32 and dpool.is_contiguous() and tuple(dpool.shape) == (M // rows_per_batch, C), \
+            f"bn_train_bwd: dpool must be contiguous f32 [{M // rows_per_batch}, {C}]"
+    d = L.BnBwdDesc()
+    d.dy, d.dpool, d.y = _p(dy), _p(dpool), _p(y)
+    dzs = []
+    for i, (z, mean, rstd, gamma, dg, db) in enumerate(branches):
+        assert z.shape == z0.shape and z.dtype == z0.dtype and z.is_contiguous()
+        _need_gpu(z, mean, rstd, gamma, dg, db)
+        assert all(t.dtype == torch.float32 and t.is_contiguous() and t.numel() == C for t in (mean, rstd, gamma, dg, db)), \
+            f"bn_train_bwd: mean / rstd / gamma / dgamma / dbeta must be contiguous f32 [{C}]"
+        dz = torch.empty_like(z)
+        dzs.append(dz)
+        d.z[i], d.mean[i], d.rstd[i], d.gamma[i] = z.data_ptr(), mean.data_ptr(), rstd.data_ptr(), gamma.data_ptr()
+        d.dgamma[i], d.dbeta[i], d.dz[i] = dg.data_ptr(), db.data_ptr(), dz.data_ptr()
+    g = torch.empty_like(z0) if want_g else None
+    d.g_out = _p(g)
+    ws = _workspace(L.lib().umr_bn_train_workspace(M, C), z0.device)
+    d.workspace, d.workspace_bytes = _p(ws), ws.numel()
+    d.rows_per_batch, d.pool_scale = rows_per_batch, pool_scale
+    d.M, d.C, d.nbranch, d.dtype = M, C, len(branches), _DT[z0.dtype]
+    L.check(L.lib().umr_bn_train_bwd_reduce(ctypes.byref(d), _stream()), "umr_bn_train_bwd_reduce")
+    L.check(L.lib().umr_bn_train_bwd_apply(ctypes.byref(d), _stream()), "umr_bn_train_bwd_apply")
+    return (dzs, g) if want_g else dzs
+
+
+def maxpool3x3s2_bwd(dy, x):
+    """gradient of maxpool3x3s2 w.r.t. its NHWC input x (saved), from dy [B, Ho, Wo, C]"""
+    _need_gpu(dy, x)
+    assert x.is_contiguous() and dy.is_contiguous() and dy.dtype == x.dtype
+    B, H, W, C = x.shape
+    assert tuple(dy.shape) == (B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C)
+    dx = torch.empty_like(x)
+    L.check(L.lib().umr_maxpool3x3s2_bwd(_p(dy), _p(x), _p(dx), B, H, W, C, _DT[x.dtype], _stream()), "umr_maxpool3x3s2_bwd")
+    return dx
+
+
+def stuff2_add(src, dst):
+    """dst[b, 2y, 2x, c] += src[b, y, x, c] (NHWC; src is the stride-2 subsampled grid of dst)"""
+    _need_gpu(src, dst)
+    assert src.is_contiguous() and dst.is_contiguous() and src.dtype == dst.dtype
+    B, H, W, C = dst.shape
+    assert tuple(src.shape) == (B, (H - 1) // 2 + 1, (W - 1) // 2 + 1, C)
+    L.check(L.lib().umr_stuff2_add(_p(src), _p(dst), B, H, W, C, _DT[dst.dtype], _stream()), "umr_stuff2_add")
+    return dst
+
+
+def bce_sigmoid(logit, label):
+    """(loss f32 [1], dlogit like logit) of BCELoss(mean)(sigmoid(logit), label), torch's clamps"""
+    _need_gpu(logit, label)
+    assert logit.dtype == label.dtype == torch.float32 and logit.is_contiguous() and label.is_contiguous() and logit.numel() == label.numel()
+    loss = torch.empty(1, dtype=torch.float32, device=logit.device)
+    dlogit = torch.empty_like(logit)
+    L.check(L.lib().umr_bce_sigmoid(_p(logit), _p(label), _p(loss), _p(dlogit), logit.numel(), _stream()), "umr_bce_sigmoid")
+    return loss, dlogit

@@ -67,7 +67,89 @@ def filter_batch(images, gt_center_fields, gt_sdf_maps, gt_saliency_maps):
     return images[keep], gt_center_fields[keep], gt_sdf_maps[keep], gt_saliency_maps[keep]
 
 
-class TrainStep:
+def rehome_params(named, offs, total, dev):
+    """Re-home parameters into ONE flat f32 buffer (p.data becomes a view at offs[name]) and allocate the matching flat gradient and
+    Adam-moment buffers: (flat_p, flat_g, m, v, {name: gradient view})."""
+    flat_p = torch.zeros(total, dtype=torch.float32, device=dev)
+    flat_g = torch.zeros(total, dtype=torch.float32, device=dev)
+    m = torch.zeros(total, dtype=torch.float32, device=dev)
+    v = torch.zeros(total, dtype=torch.float32, device=dev)
+    G = {}
+    with torch.no_grad():
+        for n, o in offs.items():
+            p = named[n]
+            view = flat_p[o:o + p.numel()].view(p.shape)
+            view.copy_(p.data)
+            p.data = view
+            G[n] = flat_g[o:o + p.numel()].view(p.shape)
+    return flat_p, flat_g, m, v, G
+
+
+class AdamState:
+    """Adam's checkpoint half and the per-iteration MultiStepLR schedule of a step object that keeps its parameters, gradients and
+    moments in flat buffers (self.net, self._offs {name: offset}, self.P {name: parameter}, self.m, self.v, self.iter, self.lr0,
+    self.betas, self.eps, self.milestones, self.gamma, self.poisoned): shared by TrainStep and ClassifierTrainStep."""
+
+    def current_lr(self):
+        lr = self.lr0
+        for ms in self.milestones:
+            if self.iter >= ms:
+                lr *= self.gamma
+        return lr
+
+    # ---- checkpoint / resume (train_objectness_net.py:118-123,268-275 and :670-678: {'model_state_dict', 'optimizer_state_dict', 'iter'})
+    def optimizer_state_dict(self):
+        """The optimizer half of the reference's checkpoint in torch.optim.Adam's own format (parameter index = position in
+        model.parameters(); parameters that never receive a gradient have no state entry, as in torch), so a checkpoint
+        written here resumes in the reference loop and vice versa."""
+        names = [n for n, _ in self.net.named_parameters()]
+        state = {}
+        if self.iter > 0:
+            for i, n in enumerate(names):
+                if n in self._offs:
+                    o, p = self._offs[n], self.P[n]
+                    state[i] = {"step": torch.tensor(float(self.iter)),
+                                "exp_avg": self.m[o:o + p.numel()].view(p.shape).clone(),
+                                "exp_avg_sq": self.v[o:o + p.numel()].view(p.shape).clone()}
+        group = {"lr": self.current_lr(), "betas": tuple(self.betas), "eps": self.eps, "weight_decay": 0, "amsgrad": False,
+                 "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
+                 "initial_lr": self.lr0, "params": list(range(len(names)))}
+        return {"state": state, "param_groups": [group]}
+
+    def load_optimizer_state_dict(self, sd, iteration=None):
+        """Restore Adam's moments (and the step count) from `optimizer_state_dict()` / a torch.optim.Adam state dict of the
+        same model.  iteration: the checkpoint's 'iter' (defaults to the stored Adam step); the learning-rate schedule here
+        is a function of that absolute iteration."""
+        names = [n for n, _ in self.net.named_parameters()]
+        assert len(sd["param_groups"]) == 1 and len(sd["param_groups"][0]["params"]) == len(names), "optimizer state of another model"
+        self.m.zero_()
+        self.v.zero_()
+        step = 0
+        for i, st in sd["state"].items():
+            n = names[int(i)]
+            if n not in self._offs:
+                continue
+            o, p = self._offs[n], self.P[n]
+            self.m[o:o + p.numel()].view(p.shape).copy_(st["exp_avg"])
+            self.v[o:o + p.numel()].view(p.shape).copy_(st["exp_avg_sq"])
+            step = max(step, int(float(st["step"])))
+        self.iter = int(iteration) if iteration is not None else step
+        assert self.iter == step or not sd["state"], "Adam step count and checkpoint iteration disagree"
+        self.poisoned = None
+
+    def lr_of_step(self, k):
+        # torch's MultiStepLR.step() runs after optimizer.step(): step k (1-based) uses the lr of k-1 completed steps
+        lr = self.lr0
+        for ms in self.milestones:
+            if k - 1 >= ms:
+                lr *= self.gamma
+        return lr
+
+    def current_lr_for_step(self):
+        return self.lr_of_step(self.iter)
+
+
+class TrainStep(AdamState):
     def __init__(self, net, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, center_field_loss_type="l2", sdf_loss_type="l1",
                  use_sdf_gradient_loss=True, use_sdf_binary_mask_loss=True, lr_milestones=(), lr_gamma=1.0, group=None,
                  grad_wire_dtype=None):
@@ -83,19 +165,7 @@ class TrainStep:
         dev = next(iter(named.values())).device
         assert dev.type == "cuda", "TrainStep needs the model on the GPU"
         offs, bounds, self.stage_bucket = flat_layout(net)
-        off = bounds[-1]
-        self.flat_p = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.flat_g = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.m = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.v = torch.zeros(off, dtype=torch.float32, device=dev)
-        self.G = {}
-        with torch.no_grad():
-            for n, o in offs.items():
-                p = named[n]
-                view = self.flat_p[o:o + p.numel()].view(p.shape)
-                view.copy_(p.data)
-                p.data = view
-                self.G[n] = self.flat_g[o:o + p.numel()].view(p.shape)
+        self.flat_p, self.flat_g, self.m, self.v, self.G = rehome_params(named, offs, bounds[-1], dev)
         self.P = {n: p for n, p in net.named_parameters()}
         self._offs = offs
         self._stage_params = {}     # stage -> [(name, offset, numel, shape)] in buffer order (PackCache.adam_and_refresh)
@@ -110,13 +180,6 @@ class TrainStep:
         self.graph_replays = 0
         self.poisoned = None        # set when a step raised in mid-flight (step()); cleared by load_optimizer_state_dict
         net._engine().cache.clear()
-
-    def current_lr(self):
-        lr = self.lr0
-        for ms in self.milestones:
-            if self.iter >= ms:
-                lr *= self.gamma
-        return lr
 
     def _body(self, images, gt_center_fields, gt_sdf_maps, gt_saliency_maps):
         """forward, loss, backward, gradient exchange, Adam (scalars from self._hyper), weight-copy refresh: the launch list of one
@@ -257,91 +320,18 @@ class TrainStep:
         if ((not self.comm.enabled or (graphs.STAGED and two)) and graphs.wanted(self.graph_mode, B * H * W, train=True, two_streams=two)
                 and ops._timer["select"] is None):
             key = (tuple(images.shape), eng.dt, ops.get_f32_mode(), torch.cuda.current_stream(images.device).cuda_stream)
-            ent = self._graphs.get(key)
-            if isinstance(ent, graphs.CAPTURE_TYPES):
-                if ent.valid():
-                    (out5,) = ent.replay(*ins)
-                    eng.cache.refreshed_by_replay(images.device)
-                    self.graph_replays += 1
-                    return out5.clone()
-                if ent.failed is None:
-                    ent = None            # the packed weights moved (state dict reloaded): warm up and capture again
-            if not isinstance(ent, graphs.CAPTURE_TYPES):
-                n = (ent or 0) + 1
-                self._graphs[key] = n
-                if n > graphs.WARMUP_CALLS:
-                    # the warm-up steps have packed every weight, built the batched refresh and sized the workspaces
-                    # small problems (the two-stream regime, engine.WgradStream): a chain of per-stage graphs on two streams; large
-                    # ones: one graph.  Every capture keeps its own pools of temporaries: a loop whose batch size keeps changing (the
-                    # reference's batch filter, train_objectness_net.py:190-207) holds at most MAX_CAPTURES of them
-                    if sum(isinstance(v, graphs.CAPTURE_TYPES) for v in self._graphs.values()) >= graphs.MAX_CAPTURES:
-                        for k_ in [k_ for k_, v in self._graphs.items() if isinstance(v, graphs.CAPTURE_TYPES)]:
-                            del self._graphs[k_]
-                        graphs.release_dropped()
-                    kind = graphs.StagedCaptured if (graphs.STAGED and two) else graphs.Captured
-                    cap = kind(self._body, ins, generation_of=eng.cache.generation, on_fail=eng.cache.purge_capture)
-                    self._graphs[key] = cap
-                    if cap.failed is None:
-                        # the capture only RECORDED the step: run it
-                        (out5,) = cap.replay(*ins)
-                        eng.cache.refreshed_by_replay(images.device)
-                        self.graph_replays += 1
-                        return out5.clone()
+            # small problems (the two-stream regime, engine.WgradStream): a chain of per-stage graphs on two streams; large ones: one graph
+            kind = graphs.StagedCaptured if (graphs.STAGED and two) else graphs.Captured
+            outs = graphs.replay_or_capture(self._graphs, key, ins,
+                                            lambda: kind(self._body, ins, generation_of=eng.cache.generation, on_fail=eng.cache.purge_capture))
+            if outs is not None:
+                eng.cache.refreshed_by_replay(images.device)
+                self.graph_replays += 1
+                return outs[0].clone()
         return self._body(*ins)[0]
-
-    # ---- checkpoint / resume (train_objectness_net.py:118-123,268-275: {'model_state_dict', 'optimizer_state_dict', 'iter'})
-    def optimizer_state_dict(self):
-        """The optimizer half of the reference's checkpoint in torch.optim.Adam's own format (parameter index = position in
-        model.parameters(); parameters that never receive a gradient have no state entry, as in torch), so a checkpoint
-        written here resumes in the reference loop and vice versa."""
-        names = [n for n, _ in self.net.named_parameters()]
-        state = {}
-        if self.iter > 0:
-            for i, n in enumerate(names):
-                if n in self._offs:
-                    o, p = self._offs[n], self.P[n]
-                    state[i] = {"step": torch.tensor(float(self.iter)),
-                                "exp_avg": self.m[o:o + p.numel()].view(p.shape).clone(),
-                                "exp_avg_sq": self.v[o:o + p.numel()].view(p.shape).clone()}
-        group = {"lr": self.current_lr(), "betas": tuple(self.betas), "eps": self.eps, "weight_decay": 0, "amsgrad": False,
-                 "maximize": False, "foreach": None, "capturable": False, "differentiable": False, "fused": None,
-                 "initial_lr": self.lr0, "params": list(range(len(names)))}
-        return {"state": state, "param_groups": [group]}
-
-    def load_optimizer_state_dict(self, sd, iteration=None):
-        """Restore Adam's moments (and the step count) from `optimizer_state_dict()` / a torch.optim.Adam state dict of the
-        same model.  iteration: the checkpoint's 'iter' (defaults to the stored Adam step); the learning-rate schedule here
-        is a function of that absolute iteration."""
-        names = [n for n, _ in self.net.named_parameters()]
-        assert len(sd["param_groups"]) == 1 and len(sd["param_groups"][0]["params"]) == len(names), "optimizer state of another model"
-        self.m.zero_()
-        self.v.zero_()
-        step = 0
-        for i, st in sd["state"].items():
-            n = names[int(i)]
-            if n not in self._offs:
-                continue
-            o, p = self._offs[n], self.P[n]
-            self.m[o:o + p.numel()].view(p.shape).copy_(st["exp_avg"])
-            self.v[o:o + p.numel()].view(p.shape).copy_(st["exp_avg_sq"])
-            step = max(step, int(float(st["step"])))
-        self.iter = int(iteration) if iteration is not None else step
-        assert self.iter == step or not sd["state"], "Adam step count and checkpoint iteration disagree"
-        self.poisoned = None
 
     def sync_from_model(self):
         """Call after model.load_state_dict(): the flat parameter buffer is the storage of the parameters, so loading writes
         through; only the packed kernel-layout weight copies have to be dropped (captured steps notice through the cache's
         generation and are captured again after two eager steps)."""
         self.net._engine().cache.clear()
-
-    def lr_of_step(self, k):
-        # torch's MultiStepLR.step() runs after optimizer.step(): step k (1-based) uses the lr of k-1 completed steps
-        lr = self.lr0
-        for ms in self.milestones:
-            if k - 1 >= ms:
-                lr *= self.gamma
-        return lr
-
-    def current_lr_for_step(self):
-        return self.lr_of_step(self.iter)
