@@ -3,11 +3,15 @@
 This is the host-side "graph": an explicit list of kernel launches (no tracing
 compiler, no autograd inside).  Activations are NHWC / [rows, channels]; weights
 are repacked from the reference's PyTorch layouts into the layouts the kernels want
-(cached per parameter version).  Reference op order and formulas:
+(cached per parameter version, packs.py).  Reference op order and formulas:
 models/dpt/vit.py:165-201 (forward_flex), :86-90 (ProjectReadout), :104-145 +
 :259-336 (reassemble), models/dpt/blocks.py:290-313 (RCU), :362-383 (fusion),
 models/dpt/models.py:74-94 (DPT.forward), models/objectness_net.py:109-135,167-183
 (heads), timm Block semantics as restated in SURVEY.md section 8c.
+
+The list is written once.  Engine.forward picks a numerics object -- PlainNumerics here (bf16, and f32 on the exact-f32-MFMA
+kernels) or engine_x3.X3Numerics (the fp32 parity mode on bf16 planes) -- and from there on names GEMMs, weight gradients and the
+few steps the modes really do differently only through it; backward uses the numerics its forward saved.
 """
 import os
 
@@ -16,7 +20,9 @@ import torch
 from . import _lib as L
 from . import graphs
 from . import ops
-from .engine_x3 import X3Path
+from .engine_x3 import X3Numerics, _drop_f, _f
+from .packs import (ParamGroup, PackCache, _ACT, _pack_conv3, _pack_conv3_dgrad, _pack_convT, _pack_convT_dgrad, _pack_linear,
+                    _pack_linear_t, _rep_bias, _unpack_conv3_grad)
 
 CONFIGS = {
     # reference wiring: models/dpt/models.py:43-47, blocks.py:24-54, vit.py:515-543
@@ -27,305 +33,6 @@ CONFIGS = {
     "dpt_large14": dict(D=1024, depth=24, heads=16, patch=14, pos_grid=37, hooks=[5, 11, 17, 23], features=[256, 512, 1024, 1024]),
     "dpt_tiny": dict(D=128, depth=4, heads=2, patch=16, pos_grid=24, hooks=[0, 1, 2, 3], features=[32, 64, 128, 128]),
 }
-
-_ACT = {None: L.ACT_NONE, "tanh": L.ACT_TANH, "sine": ops.ACT_SINE}
-
-
-class ParamGroup:
-    """Several parameters seen by PackCache.get as one: the key of a pack derived from all of them (the collapsed head's weight
-    algebra reads eight tensors) -- its version is the tuple of theirs, so a change of any one misses."""
-
-    def __init__(self, params):
-        self.ps = tuple(params)
-        self.is_cuda, self.device = self.ps[0].is_cuda, self.ps[0].device
-
-    @property
-    def _version(self):
-        return tuple(p._version for p in self.ps)
-
-    def data_ptr(self):
-        return tuple(p.data_ptr() for p in self.ps)
-
-
-class PackCache:
-    """Kernel-layout copies of parameters, rebuilt when the parameter changes.
-
-    Stream-safe: an entry is built by kernels enqueued on whatever stream touches it first and is published to this host-side
-    dict at once, so a consumer on ANOTHER stream (reasoning.sweep_proposals deals batches to several streams) could launch
-    a GEMM that reads the packed buffer before the pack kernel has run.  Every entry therefore carries an event recorded
-    right after its build; a hit from a stream that has not yet ordered itself after that event waits on it first (once per
-    stream and entry -- afterwards the stream's own order covers it)."""
-
-    def __init__(self):
-        self._c = {}           # key -> [version, value, event, synced streams, recipe, param]: replayable packs
-        self._o = {}           # same without a recipe: rebuilt lazily after refresh()
-        self._replay = {}      # tag -> (launcher, keys) of a batched refresh (None: all entries), built on first use
-        # A captured graph holds the ADDRESSES of the copies it read: gen_c counts changes of the replayable set (and of the batched
-        # refresh's table), gen_o changes of the rest.  A capture depends on gen_o only if it read such an entry that it did not
-        # build itself (a capture rebuilds its own on every replay): generation(store)
-        self.gen_c = 0
-        self.gen_o = 0
-        self._epoch = None     # (event, synced streams) of the last refresh that ran inside a graph replay (graphs.py)
-
-    def get(self, key, param, build, recipe_fn=None):
-        """recipe_fn(recorded launches, value) -> replay recipe or None: for packs whose replayable form is not the launch that
-        built them (the bf16-plane weights: built as f32 pack + split, refreshed as one permute straight into planes)"""
-        ver = (param._version, param.data_ptr())
-        hit = self._c.get(key) or self._o.get(key)
-        cap = graphs.capturing()
-        sid = ops._stream_id(param.device.index) if param.is_cuda else None    # raw handle: no Stream object on the hit path
-        if hit is not None and hit[0] == ver:
-            if cap and key in self._o and hit[6] is not graphs.capture_store():
-                graphs.capture_store()["hit_o"] = True
-            # (inside a capture nothing from before it is pending -- graphs.Captured synchronises first -- and an event wait on
-            # work outside the capture must not be recorded into it)
-            if sid is not None and not cap:
-                if hit[2] is not None and sid not in hit[3]:
-                    torch.cuda.current_stream(param.device).wait_event(hit[2])
-                    hit[3].add(sid)
-                if self._epoch is not None and sid not in self._epoch[1]:
-                    torch.cuda.current_stream(param.device).wait_event(self._epoch[0])
-                    self._epoch[1].add(sid)
-            return hit[1]
-        st = torch.cuda.current_stream(param.device) if param.is_cuda else None
-        # record what the build launches: a pack that is exactly ONE permute / cast into the returned tensor can be replayed by
-        # refresh() (every pack helper below is); anything else is rebuilt lazily after a refresh
-        rec = []
-        prev, ops._pack_recorder = ops._pack_recorder, rec
-        try:
-            val = build()
-        finally:
-            ops._pack_recorder = prev
-        # replayable only if the recorded source IS the parameter's storage: a pack helper that had to make a temporary copy first
-        # (reshape of a non-contiguous parameter) would be re-packed from that stale temporary forever
-        if recipe_fn is not None:
-            recipe = recipe_fn(rec, val)
-            if recipe is not None and recipe[0].untyped_storage().data_ptr() != param.untyped_storage().data_ptr():
-                recipe = None
-        else:
-            recipe = rec[0] if (len(rec) == 1 and torch.is_tensor(val) and rec[0][1].data_ptr() == val.data_ptr()
-                                and rec[0][0].untyped_storage().data_ptr() == param.untyped_storage().data_ptr()) else None
-        ev = None
-        if st is not None and not cap:
-            ev = torch.cuda.Event()
-            ev.record(st)
-        entry = [ver, val, ev, {sid}, recipe, param, (graphs.capture_store() if cap else None)]
-        if self._c.pop(key, None) is not None:
-            self._replay = {}         # the batched refreshes were built over the dropped entry
-            self.gen_c += 1
-        if self._o.pop(key, None) is not None:
-            self.gen_o += 1
-        if recipe is not None and st is not None:
-            self._c[key] = entry
-            self._replay = {}
-            self.gen_c += 1
-        else:
-            self._o[key] = entry
-            self.gen_o += 1
-        return val
-
-    def generation(self, store=None):
-        """validity stamp of a capture whose scratch dict is `store` (graphs.Captured)"""
-        return (self.gen_c, self.gen_o if (store is None or store.get("hit_o")) else None)
-
-    def clear(self):
-        self._c.clear()
-        self._o.clear()
-        self._replay = {}
-        self._epoch = None
-        self.gen_c += 1
-        self.gen_o += 1
-
-    def purge_capture(self, store):
-        """A HIP-graph capture whose scratch dict is `store` FAILED: the packs it built were only recorded, never executed -- their
-        buffers (in the capture's private pool) hold nothing, yet they sit in the cache under the parameters' current versions.
-        Drop them, so the eager path that takes over re-packs (graphs.Captured calls this from its failure path)."""
-        dead_c = [k for k, e in self._c.items() if e[6] is store]
-        dead_o = [k for k, e in self._o.items() if e[6] is store]
-        for k in dead_c:
-            del self._c[k]
-        for k in dead_o:
-            del self._o[k]
-        if dead_c:
-            self._replay = {}
-            self.gen_c += 1
-        if dead_o:
-            self.gen_o += 1
-        return len(dead_c) + len(dead_o)
-
-    def refresh(self, tag=None, select=None):
-        """The parameters were updated IN PLACE by a kernel torch does not see (TrainStep's Adam launch): re-run every pack into
-        its existing destination in ONE launch (umr_permute4_batched) instead of dropping the copies and re-packing ~180
-        weights one launch each during the next step.  Entries that are not a single permute are dropped (rebuilt lazily).
-        tag / select(key): refresh only the entries select() accepts (one launch per tag: TrainStep updates and refreshes stage
-        by stage, beside the rest of backward); the caller ends the round of partial refreshes with refresh_done()."""
-        if tag is None:
-            self.refresh_done()
-        if not self._c:
-            return
-        if tag not in self._replay:
-            assert not graphs.capturing(), "PackCache.refresh: the batched refresh must be built before a capture (warm-up steps)"
-            keys = [k for k in self._c if select is None or select(k)]
-            self._replay[tag] = (ops.permute4_batched([self._c[k][4] for k in keys]) if keys else None, keys)
-        launch, keys = self._replay[tag]
-        if launch is None:
-            return
-        if any(self._c[k][5].data_ptr() != self._c[k][0][1] for k in keys):   # a parameter's storage moved: the recipes are stale
-            self.clear()
-            return
-        launch()
-        if graphs.capturing():
-            return                     # the replaying caller publishes the refresh with refreshed_by_replay()
-        st = torch.cuda.current_stream(self._c[keys[0]][5].device)
-        ev = torch.cuda.Event()
-        ev.record(st)
-        for k in keys:
-            e = self._c[k]
-            e[0] = (e[5]._version, e[5].data_ptr())
-            e[2], e[3] = ev, {st.cuda_stream}
-
-    def adam_and_refresh(self, tag, select, stage_params, lo, hi, bufs, hyper):
-        """Optimizer step of the flat-buffer slice [lo, hi) AND the refresh of its packed copies, with the copies of its Linear
-        weights written by the optimizer launch itself (ops.adam_pack / umr_adam_pack_step: the refresh pass that re-read those f32
-        weights is gone; the other packs of the stage -- conv layouts, plane forms -- keep the batched permute).
-        stage_params: [(name, element offset, numel, shape)] of the slice in buffer order; bufs = (flat p, g, m, v); hyper: device
-        scalars of umr_adam_set_hyper.  Returns False (nothing launched) when no weight of the stage has a bf16 [N,K] / [K,N] copy
-        -- the caller then runs the two-launch form.  Bit-identical to it (tests/test_train_gpu.py)."""
-        rk = ("adam", tag)
-        if rk not in self._replay:
-            assert not graphs.capturing(), "PackCache.adam_and_refresh: the tables must be built before a capture (warm-up steps)"
-            keys = [k for k in self._c if select is None or select(k)]
-            by_name = {}
-            for k in keys:
-                by_name.setdefault(k[0], {})[k[1]] = k
-            flat_p, flat_g, flat_m, flat_v = bufs
-            entries, fused, cur = [], set(), lo
-            for name, off, numel, shape in stage_params:
-                kinds = by_name.get(name, {})
-                ok = (len(shape) == 2 and shape[0] % 8 == 0 and shape[1] % 4 == 0 and off % 4 == 0 and kinds and set(kinds) <= {"lin", "lin_t"}
-                      and all(torch.is_tensor(self._c[k][1]) and self._c[k][1].dtype == torch.bfloat16 and self._c[k][1].is_contiguous()
-                              for k in kinds.values()))
-                if ok:
-                    dl = self._c[kinds["lin"]][1] if "lin" in kinds else None
-                    dt_ = self._c[kinds["lin_t"]][1] if "lin_t" in kinds else None
-                    ok = (dl is None or tuple(dl.shape) == tuple(shape)) and (dt_ is None or tuple(dt_.shape) == (shape[1], shape[0]))
-                if not ok:
-                    continue
-                if cur < off:
-                    entries.append(("plain",) + tuple(b[cur:off] for b in bufs))
-                entries.append(("weight",) + tuple(b[off:off + numel].view(shape) for b in bufs) + (dl, dt_))
-                fused.update(kinds.values())
-                cur = off + numel
-            if not fused:
-                self._replay[rk] = None
-            else:
-                if cur < hi:
-                    entries.append(("plain",) + tuple(b[cur:hi] for b in bufs))
-                rest = [k for k in keys if k not in fused]
-                self._replay[rk] = (ops.adam_pack(entries, hyper), ops.permute4_batched([self._c[k][4] for k in rest]) if rest else None, keys)
-        rec = self._replay[rk]
-        if rec is None:
-            return False
-        launch_adam, launch_rest, keys = rec
-        if any(self._c[k][5].data_ptr() != self._c[k][0][1] for k in keys):   # a parameter's storage moved: the tables are stale
-            self.clear()
-            return False
-        launch_adam()
-        if launch_rest is not None:
-            launch_rest()
-        if graphs.capturing():
-            return True                # the replaying caller publishes the refresh with refreshed_by_replay()
-        st = torch.cuda.current_stream(self._c[keys[0]][5].device)
-        ev = torch.cuda.Event()
-        ev.record(st)
-        for k in keys:
-            e = self._c[k]
-            e[0] = (e[5]._version, e[5].data_ptr())
-            e[2], e[3] = ev, {st.cuda_stream}
-        return True
-
-    def refresh_done(self):
-        """after the last (partial) refresh of a round: the copies that cannot be replayed are dropped (rebuilt on next use).
-        Inside a capture, entries the capture built itself go silently (each of its replays rebuilds them); every OTHER dropped entry
-        -- e.g. the collapsed head's weights an evaluation call cached between a TrainStep's warm-up and its capturing step -- counts
-        as a change of the set, so an inference capture that read it (hit_o) is invalidated instead of replaying from freed memory."""
-        if self._o:
-            cur = graphs.capture_store() if graphs.capturing() else None
-            foreign = cur is None or any(e[6] is not cur for e in self._o.values())
-            self._o.clear()
-            if foreign:
-                self.gen_o += 1
-
-    def synced_with(self, stream):
-        """`stream` has waited for the stream(s) the refreshes ran on (a join): its later launches need no per-entry event wait"""
-        sid = stream.cuda_stream
-        for e in self._c.values():
-            e[3].add(sid)
-
-    def refreshed_by_replay(self, device):
-        """A graph replay on the current stream has just re-run the optimizer step and the refresh: a consumer on another stream
-        orders itself after it (one event for the whole cache instead of one per entry).  The replay updated the parameters on
-        the device without running this class's host code, so what refresh_done() does after an eager step is done here: EVERY copy
-        that cannot be replayed is stale in this host-side dict now and is dropped -- those built outside a capture (the collapsed head's
-        weights an evaluation call cached between two training steps) and those an inference capture built inside itself: that capture
-        holds the addresses and rewrites them on each of its replays, but a cache HIT by anybody else (an eager call of another shape,
-        a second capture) would read what the first graph's LAST replay wrote, i.e. weights one or more steps old (round-5 advisor)."""
-        if self._o:
-            self._o.clear()
-            self.gen_o += 1
-        st = torch.cuda.current_stream(device)
-        ev = torch.cuda.Event()
-        ev.record(st)
-        self._epoch = (ev, {st.cuda_stream})
-
-
-def _pack_linear(w, dt):  # [N,K] -> [N,K] T
-    return ops.cast(w.detach().reshape(w.shape[0], -1), dt)
-
-
-def _pack_linear_t(w2d, dt):  # [N,K] (possibly strided rows) -> [K,N] T
-    N, K = w2d.shape
-    out = torch.empty((K, N), dtype=dt, device=w2d.device)
-    return ops.permute4(w2d, out, (1, 1, K, N), (0, 0, w2d.stride(1), w2d.stride(0)), src_offset=0)
-
-
-def _pack_conv3(w, dt):  # [co,ci,3,3] -> [co][ky][kx][ci]
-    co, ci = w.shape[0], w.shape[1]
-    st = w.stride()
-    out = torch.empty((co, 9 * ci), dtype=dt, device=w.device)
-    return ops.permute4(w.detach(), out, (co, 3, 3, ci), (st[0], st[2], st[3], st[1]))
-
-
-def _pack_conv3_dgrad(w, dt):  # [co,ci,3,3] -> [ci][2-ky][2-kx][co]
-    co, ci = w.shape[0], w.shape[1]
-    st = w.stride()
-    out = torch.empty((ci, 9 * co), dtype=dt, device=w.device)
-    return ops.permute4(w.detach(), out, (ci, 3, 3, co), (st[1], -st[2], -st[3], st[0]), src_offset=2 * st[2] + 2 * st[3])
-
-
-def _unpack_conv3_grad(dwp, grad_out):  # [co][ky][kx][ci] f32 -> [co,ci,3,3] f32
-    co, ci = grad_out.shape[0], grad_out.shape[1]
-    return ops.permute4(dwp, grad_out, (co, ci, 3, 3), (9 * ci, 1, 3 * ci, ci))
-
-
-def _pack_convT(w, dt):  # ConvTranspose2d [ci,co,s,s] -> [(i,j,co)][ci]
-    ci, co, s, _ = w.shape
-    st = w.stride()
-    out = torch.empty((s * s * co, ci), dtype=dt, device=w.device)
-    return ops.permute4(w.detach(), out, (s, s, co, ci), (st[2], st[3], st[1], st[0]))
-
-
-def _pack_convT_dgrad(w, dt):  # -> [ci][(i,j,co)]
-    ci, co, s, _ = w.shape
-    st = w.stride()
-    out = torch.empty((ci, s * s * co), dtype=dt, device=w.device)
-    return ops.permute4(w.detach(), out, (ci, s, s, co), (st[0], st[2], st[3], st[1]))
-
-
-def _rep_bias(b, reps):
-    out = torch.empty(reps * b.numel(), dtype=torch.float32, device=b.device)
-    return ops.permute4(b.detach(), out, (1, 1, reps, b.numel()), (0, 0, 0, 1))
-
 
 _FUSE_HEAD_OUT = True   # the heads' 1024 -> {1,2} output layer in the epilogue of the GEMM before it (tests switch it off)
 # A 1x1 convolution and a bilinear resize commute exactly (both linear, one per pixel across channels, the other per channel across
@@ -394,7 +101,107 @@ class WgradStream:
         return pixels <= graphs.AUTO_MAX_PIXELS
 
 
-class Engine(X3Path):
+class PlainNumerics:
+    """bf16 mode and the exact-f32-MFMA mode (UMR_F32_X3=0) behind Engine.forward / backward: a value is a plain tensor in the
+    compute dtype and every GEMM is one ops.gemm_nt / gemm_tn launch.  Same interface as engine_x3.X3Numerics, one object per
+    call: e = the Engine, P = its parameters."""
+
+    def __init__(self, e, P):
+        self.e, self.P = e, P
+
+    def val(self, t):
+        return t
+
+    def to_dt(self, t):
+        """an f32 tensor in the compute dtype"""
+        return t if self.e.dt == torch.float32 else ops.cast(t, self.e.dt)
+
+    def mm(self, A, wname, kind, bias=None, *, conv=0, act=L.ACT_NONE, want="f", mask=None, dgelu=None, aux=None, aux2=None,
+           rowbias=None, rows_per_batch=0, c2_mode=0, c2_want="f", out=None, c_remap=None, aux_mod=0):
+        """epi(A . W^T) with W = parameter `wname` in layout `kind` (Engine._w).  mask / dgelu / aux: the ONE [M, N] epilogue operand
+        (keep where > 0 / times GELU'(.) / add).  want / c2_want (a format to ask for) mean nothing here."""
+        a_t = mask if mask is not None else (dgelu if dgelu is not None else aux)
+        return ops.gemm_nt(A, self.e._w(self.P, wname, kind), bias, out=out, aux=a_t, aux2=aux2, rowbias=rowbias,
+                           rows_per_batch=rows_per_batch, act=act, mask_relu=mask is not None, mask_dgelu=dgelu is not None,
+                           c2_mode=c2_mode, conv=conv, c_remap=c_remap, aux_mod=aux_mod)
+
+    def wgrad(self, dY, X, dW, dbias=None, *, conv=0, wg=None, then=None):
+        """dW = dY^T X (X NHWC with conv); with wg (a WgradStream) the launch and `then(dW)` go to the weight-gradient stream"""
+        def launch():
+            r = ops.gemm_tn(dY, X, dW=dW, dbias=dbias, conv=conv)
+            if then is not None:
+                then(r)
+            return r
+        return launch() if wg is None else wg.run(launch, dY, X)
+
+    # ------------------------------------------------------------------ the steps of the schedule that are this mode's own
+    def layernorm(self, x, gamma, beta):
+        return ops.layernorm_fwd(x, gamma, beta)
+
+    def readout(self, tok, wname, bias, save, B, g, Nt, D):
+        """ProjectReadout (vit.py:86-90) on the hooked tokens [B*Nt, D]: the GEMM gathers the token rows itself, the class-token
+        half of the weight [D, 2D] adds a per-image row bias; both halves are column slices of ONE pack"""
+        P, dt = self.P, self.e.dt
+        w_full = self.e.cache.get((wname, "lin", dt), P[wname], lambda: _pack_linear(P[wname], dt))  # [D, 2D]
+        rb = ops.gemm_nt(tok, w_full[:, D:], bias, M=B, lda=Nt * D, out_f32=True)  # cls part + bias
+        if save:
+            r, rpre = ops.gemm_nt(tok, w_full[:, :D], None, rowbias=rb, rows_per_batch=g, act=L.ACT_GELU, c2_mode=2, M=B * g,
+                                  a_remap=(g, Nt, 1))
+        else:
+            r, rpre = ops.gemm_nt(tok, w_full[:, :D], None, rowbias=rb, rows_per_batch=g, act=L.ACT_GELU, M=B * g,
+                                  a_remap=(g, Nt, 1)), None
+        return dict(r=r, rpre=rpre)
+
+    def readout_wgrad(self, d_rpre, rs, tok, dW, B, g, Nt):
+        """token half of the readout weight's gradient: the GEMM gathers the token rows"""
+        ops.gemm_tn(d_rpre, tok, dW=dW, x_remap=(g, Nt, 1), M=B * g)
+
+    def hook_grad(self, d_rpre, sB, wname, dx, B, g, Nt, D):
+        """the readout's data gradient added into the token gradient dx [B*Nt, D] (created here at the last hook)"""
+        dt = self.e.dt
+        w = self.P[wname].detach()
+        wa_t = self.e.cache.get((wname, "lin_t_a", dt), self.P[wname], lambda: _pack_linear_t(w[:, :D], dt))
+        wb_t = self.e.cache.get((wname, "lin_t_b", dt), self.P[wname], lambda: _pack_linear_t(w[:, D:], dt))
+        if dx is None:
+            dx = torch.zeros((B * Nt, D), dtype=dt, device=sB.device)
+        ops.gemm_nt(d_rpre, wa_t, None, out=dx, aux=dx, c_remap=(g, Nt, 1))
+        cls_rows = dx.view(B, Nt * D)[:, :D]  # token 0 of every image: row stride Nt*D
+        ops.gemm_nt(sB, wb_t, None, out=cls_rows, aux=cls_rows)
+        return dx
+
+    def head_resize(self, h1l, shape_low, H, W, relu):
+        """resize(W1 path + b1), then the ReLU"""
+        return ops.bilinear_fwd(h1l.view(*shape_low, -1), H, W, True, relu=relu).view(shape_low[0] * H * W, -1)
+
+    def head_tail(self, h2, w3name, b3, w4, b4, act, final, keep, pre, B, H, W):
+        """third and output layer of a factored head: (out, h3, pre-activation of the output or None)"""
+        w3 = self.e._w(self.P, w3name, "lin")
+        if _FUSE_HEAD_OUT and ops.gemm_nt(h2, w3, b3, act=act, query_rowreduce=True):
+            # the 1024 -> {1,2} output layer rides in the epilogue of the GEMM that produces its input (one read of
+            # h3 saved); without saved activations (inference) h3 is not written at all
+            h3, parts = ops.gemm_nt(h2, w3, b3, act=act, red_w=w4.contiguous(), no_store=not keep)
+            out = ops.head_out_finish(parts, b4, B, H, W, final)
+            return out, h3, (ops.head_out_finish(parts, b4, B, H, W, L.ACT_NONE) if pre else None)
+        h3 = ops.gemm_nt(h2, w3, b3, act=act)
+        out = ops.head_out_fwd(h3, w4, b4, B, H, W, final)
+        return out, h3, (ops.head_out_fwd(h3, w4, b4, B, H, W, L.ACT_NONE) if pre else None)
+
+    def heads_backward(self, S, d_center, d_sdf, G, wgrad_lin, wgrad_c3, done):
+        """Backward of both heads with their first layers' gradients side by side in one buffer (Engine._heads_backward_lowres /
+        _fullres); done() closes the stage.  Returns the gradient of the map the last fusion block wrote."""
+        e = self.e
+        heads_bwd = e._heads_backward_lowres if S.get("path") is not None else e._heads_backward_fullres
+        dpath = heads_bwd(self.P, S, d_center, d_sdf, G, wgrad_lin, wgrad_c3)
+        done()
+        return dpath
+
+    def patch_wgrad(self, dx, patches, dW, dbias, B, g, Nt):
+        """gradient of the patch-embedding weight (dW None: returned, in the padded layout of `patches`); the GEMM skips the
+        class-token rows of dx"""
+        return ops.gemm_tn(dx, patches, dW=dW, dbias=dbias, dy_remap=(g, Nt, 1), M=B * g)
+
+
+class Engine:
     def __init__(self, cfg, head_layouts, compute_dtype=torch.float32, collapse_linear_heads=False, linear_head_backward=None):
         self.cfg = cfg
         # backward of a head without non-linearities between its convs (objectness_net.py:119-142): "algebraic" = exact gradients of
@@ -599,8 +406,11 @@ class Engine(X3Path):
         object_reasoning.py:379-487 read the boundary-distance map alone, and the centre head is most of a 128x128 crop's forward."""
         cfg, dt = self.cfg, self.dt
         assert not (skip and save), "skip: inference only"
-        if dt == torch.float32 and ops.get_f32_mode() in ("x3", "x3_fast"):
-            return self.forward_x3(P, images, save, skip)      # fp32 parity mode on the bf16-plane kernels (engine_x3.py)
+        # fp32 parity mode on the bf16-plane kernels (engine_x3.py), or plain tensors in the compute dtype: the launch list below
+        # does not ask which
+        nx = (X3Numerics if dt == torch.float32 and ops.get_f32_mode() in ("x3", "x3_fast") else PlainNumerics)(self, P)
+        mm, val = nx.mm, nx.val
+        b_ = lambda name: self._f32(P, name)
         assert images.is_cuda and images.dtype == torch.float32 and images.dim() == 4 and images.shape[1] == 3
         images = images.contiguous()
         B, _, H, W = images.shape
@@ -609,48 +419,51 @@ class Engine(X3Path):
         assert gh >= 1 and gw >= 1
         g, Nt = gh * gw, gh * gw + 1
         m = "backbone.pretrained.model."
-        S = {"B": B, "H": H, "W": W, "gh": gh, "gw": gw} if save else None
+        dev = images.device
+        S = {"B": B, "H": H, "W": W, "gh": gh, "gw": gw, "numerics": type(nx)} if save else None
 
         # ---- patch embed + cls + pos (vit.py:168-193)
         G = cfg["pos_grid"]
-        pos = self._f32(P, m + "pos_embed")[0]  # [1+G*G, D]
+        pos = b_(m + "pos_embed")[0]  # [1+G*G, D]
         if (gh, gw) != (G, G):
             pos_grid = ops.bilinear_fwd(pos[1:].reshape(1, G, G, D), gh, gw, False).reshape(g, D)
         else:
             pos_grid = pos[1:]
-        pos_t = pos_grid if dt == torch.float32 else ops.cast(pos_grid.contiguous(), dt)
+        pos_t = nx.to_dt(pos_grid.contiguous())
         K = 3 * p * p
         ldk = (K + 7) // 8 * 8
-        patches = ops.patchify(images, p, dt, ldk)
-        wp = self._w(P, m + "patch_embed.proj.weight", "lin")
-        if ldk != K:
-            wpad = torch.zeros((D, ldk), dtype=dt, device=images.device)
+        patches = val(ops.patchify(images, p, dt, ldk))
+        tokens = torch.empty((B * Nt, D), dtype=dt, device=dev)
+        if ldk == K:
+            mm(patches, m + "patch_embed.proj.weight", "lin", b_(m + "patch_embed.proj.bias"), out=tokens, aux=pos_t, aux_mod=g,
+               c_remap=(g, Nt, 1))
+        else:
+            # rows padded to a multiple of 8 elements (patch 14): zero columns on the weight
+            wp = self._w(P, m + "patch_embed.proj.weight", "lin")
+            wpad = torch.zeros((D, ldk), dtype=dt, device=dev)
             wpad[:, :K] = wp
-            wp = wpad
-        tokens = torch.empty((B * Nt, D), dtype=dt, device=images.device)
-        ops.gemm_nt(patches, wp, self._f32(P, m + "patch_embed.proj.bias"), out=tokens, aux=pos_t.contiguous(), aux_mod=g,
-                    c_remap=(g, Nt, 1))
-        ops.fill_cls(tokens, self._f32(P, m + "cls_token").reshape(-1), pos[0].contiguous(), B, Nt * D, D)
+            ops.gemm_nt(_f(patches), wpad, b_(m + "patch_embed.proj.bias"), out=tokens, aux=pos_t, aux_mod=g, c_remap=(g, Nt, 1))
+        ops.fill_cls(tokens, b_(m + "cls_token").reshape(-1), pos[0].contiguous(), B, Nt * D, D)
         if save:
             S["patches"] = patches
 
         # ---- transformer blocks (timm Block; only up to the last hooked block: later ones feed nothing, vit.py:107)
+        # what only feeds GEMMs is asked for as want="p"; what LayerNorm, attention or a residual reads is taken as f32 (_f)
         x = tokens
-        acts = []
-        blocks = []
+        acts, blocks = [], []
         for i in range(max(cfg["hooks"]) + 1):
             b = m + f"blocks.{i}."
-            ln1, mean1, rstd1 = ops.layernorm_fwd(x, self._f32(P, b + "norm1.weight"), self._f32(P, b + "norm1.bias"))
-            qkv = ops.gemm_nt(ln1, self._w(P, b + "attn.qkv.weight", "lin"), self._f32(P, b + "attn.qkv.bias"))
+            ln1, mean1, rstd1 = nx.layernorm(x, b_(b + "norm1.weight"), b_(b + "norm1.bias"))
+            qkv = _f(mm(ln1, b + "attn.qkv.weight", "lin", b_(b + "attn.qkv.bias")))
             att, lse = ops.attention_fwd(qkv, B, Nt, heads, need_lse=save)
-            x1 = ops.gemm_nt(att, self._w(P, b + "attn.proj.weight", "lin"), self._f32(P, b + "attn.proj.bias"), aux=x)
-            ln2, mean2, rstd2 = ops.layernorm_fwd(x1, self._f32(P, b + "norm2.weight"), self._f32(P, b + "norm2.bias"))
+            att = val(att)
+            x1 = _f(mm(att, b + "attn.proj.weight", "lin", b_(b + "attn.proj.bias"), aux=x))
+            ln2, mean2, rstd2 = nx.layernorm(x1, b_(b + "norm2.weight"), b_(b + "norm2.bias"))
             if save:
-                h, hpre = ops.gemm_nt(ln2, self._w(P, b + "mlp.fc1.weight", "lin"), self._f32(P, b + "mlp.fc1.bias"),
-                                      act=L.ACT_GELU, c2_mode=2)
+                h, hpre = mm(ln2, b + "mlp.fc1.weight", "lin", b_(b + "mlp.fc1.bias"), act=L.ACT_GELU, c2_mode=2, want="p")
             else:
-                h, hpre = ops.gemm_nt(ln2, self._w(P, b + "mlp.fc1.weight", "lin"), self._f32(P, b + "mlp.fc1.bias"), act=L.ACT_GELU), None
-            x2 = ops.gemm_nt(h, self._w(P, b + "mlp.fc2.weight", "lin"), self._f32(P, b + "mlp.fc2.bias"), aux=x1)
+                h, hpre = mm(ln2, b + "mlp.fc1.weight", "lin", b_(b + "mlp.fc1.bias"), act=L.ACT_GELU, want="p"), None
+            x2 = _f(mm(h, b + "mlp.fc2.weight", "lin", b_(b + "mlp.fc2.bias"), aux=x1))
             if save:
                 blocks.append(dict(x=x, mean1=mean1, rstd1=rstd1, ln1=ln1, qkv=qkv, att=att, lse=lse, x1=x1, mean2=mean2,
                                    rstd2=rstd2, ln2=ln2, hpre=hpre, h=h))
@@ -664,69 +477,61 @@ class Engine(X3Path):
         # ---- readout + reassemble (vit.py:86-90,104-145,259-336)
         pp = "backbone.pretrained."
         Fs = cfg["features"]
-        layers = []
-        re_saved = []
+        layers, re_saved = [], []
         for k in range(4):
             a = pp + f"act_postprocess{k + 1}."
-            wname = a + "0.project.0.weight"
-            w_full = self.cache.get((wname, "lin", dt), P[wname], lambda: _pack_linear(P[wname], dt))  # [D, 2D]
-            tok = acts[k]
-            rb = ops.gemm_nt(tok, w_full[:, D:], self._f32(P, a + "0.project.0.bias"), M=B, lda=Nt * D, out_f32=True)  # cls part + bias
-            if save:
-                r, rpre = ops.gemm_nt(tok, w_full[:, :D], None, rowbias=rb, rows_per_batch=g, act=L.ACT_GELU, c2_mode=2, M=B * g,
-                                      a_remap=(g, Nt, 1))
-            else:
-                r, rpre = ops.gemm_nt(tok, w_full[:, :D], None, rowbias=rb, rows_per_batch=g, act=L.ACT_GELU, M=B * g,
-                                      a_remap=(g, Nt, 1)), None
-            f = ops.gemm_nt(r, self._w(P, a + "3.weight", "lin"), self._f32(P, a + "3.bias"))  # [B*g, F]
+            rs = nx.readout(acts[k], a + "0.project.0.weight", b_(a + "0.project.0.bias"), save, B, g, Nt, D)
             F_ = Fs[k]
+            # [B*g, F]; f32 where the stride-2 conv reads it
+            f = mm(rs["r"], a + "3.weight", "lin", b_(a + "3.bias"), want=("f" if k == 3 else "p"))
             if k in (0, 1):
                 s = 4 if k == 0 else 2
                 bname = a + "4.bias"
                 brep = self.cache.get((bname, "rep", s), P[bname], lambda: _rep_bias(P[bname], s * s))
-                y = ops.gemm_nt(f, self._w(P, a + "4.weight", "ct"), brep)
-                lay = ops.pixel_shuffle(y, B, gh, gw, s, F_)
+                y = _f(mm(f, a + "4.weight", "ct", brep))
+                lay = val(ops.pixel_shuffle(y, B, gh, gw, s, F_))
             elif k == 2:
                 lay = f.view(B, gh, gw, F_)
             else:
-                lay = ops.gemm_nt(f.view(B, gh, gw, F_), self._w(P, a + "4.weight", "c3"), self._f32(P, a + "4.bias"), conv=2)
+                lay = mm(f.view(B, gh, gw, F_), a + "4.weight", "c3", b_(a + "4.bias"), conv=2)
                 lay = lay.view(B, (gh - 1) // 2 + 1, (gw - 1) // 2 + 1, F_)
             layers.append(lay)
             if save:
-                re_saved.append(dict(r=r, rpre=rpre, f=f))
+                rs["f"] = f
+                re_saved.append(rs)
         if save:
             S["re"] = re_saved
-            S["layers"] = layers
 
         # ---- scratch convs + refinenets (models.py:80-91, blocks.py:290-383)
         sc = "backbone.scratch."
         rn, rn_relu = [], []
         for k in range(4):
             lay = layers[k]
-            o, orl = ops.gemm_nt(lay, self._w(P, sc + f"layer{k + 1}_rn.weight", "c3"), None, conv=1, c2_mode=1)
-            rn.append(o.view(lay.shape[0], lay.shape[1], lay.shape[2], 256))
-            rn_relu.append(orl.view_as(rn[-1]))
+            o, orl = mm(lay, sc + f"layer{k + 1}_rn.weight", "c3", None, conv=1, c2_mode=1, c2_want="p")
+            shp = (lay.shape[0], lay.shape[1], lay.shape[2], 256)
+            rn.append(o.view(*shp))
+            rn_relu.append(orl.view(*shp))
         fus_saved = {}
         path = None
         for k in (4, 3, 2, 1):
             r_ = sc + f"refinenet{k}."
             x1_, x1_relu = rn[k - 1], rn_relu[k - 1]
             nb, hh, ww, _ = x1_.shape
+            shp = (nb, hh, ww, 256)
             fs = {}
             if path is None:
                 s_, s_relu = x1_, x1_relu
             else:
                 assert path.shape == x1_.shape, "fusion skip/size mismatch"
-                t1 = ops.gemm_nt(x1_relu, self._w(P, r_ + "resConfUnit1.conv1.weight", "c3"),
-                                 self._f32(P, r_ + "resConfUnit1.conv1.bias"), conv=1, act=L.ACT_RELU).view_as(x1_)
-                s_, s_relu = ops.gemm_nt(t1, self._w(P, r_ + "resConfUnit1.conv2.weight", "c3"),
-                                         self._f32(P, r_ + "resConfUnit1.conv2.bias"), conv=1, aux=x1_, aux2=path, c2_mode=1)
-                s_, s_relu = s_.view_as(x1_), s_relu.view_as(x1_)
+                t1 = mm(x1_relu, r_ + "resConfUnit1.conv1.weight", "c3", b_(r_ + "resConfUnit1.conv1.bias"), conv=1, act=L.ACT_RELU,
+                        want="p").view(*shp)
+                s_, s_relu = mm(t1, r_ + "resConfUnit1.conv2.weight", "c3", b_(r_ + "resConfUnit1.conv2.bias"), conv=1, aux=x1_, aux2=path,
+                                c2_mode=1, c2_want="p")
+                s_, s_relu = s_.view(*shp), s_relu.view(*shp)
                 fs.update(x1_relu=x1_relu, t1=t1)
-            t2 = ops.gemm_nt(s_relu, self._w(P, r_ + "resConfUnit2.conv1.weight", "c3"),
-                             self._f32(P, r_ + "resConfUnit2.conv1.bias"), conv=1, act=L.ACT_RELU).view_as(x1_)
-            u = ops.gemm_nt(t2, self._w(P, r_ + "resConfUnit2.conv2.weight", "c3"),
-                            self._f32(P, r_ + "resConfUnit2.conv2.bias"), conv=1, aux=s_).view_as(x1_)
+            t2 = mm(s_relu, r_ + "resConfUnit2.conv1.weight", "c3", b_(r_ + "resConfUnit2.conv1.bias"), conv=1, act=L.ACT_RELU,
+                    want="p").view(*shp)
+            u = mm(t2, r_ + "resConfUnit2.conv2.weight", "c3", b_(r_ + "resConfUnit2.conv2.bias"), conv=1, aux=s_).view(*shp)
             if k > 1 and cfg["patch"] != 16:
                 nxt = rn[k - 2].shape
                 Ho, Wo = nxt[1], nxt[2]  # patch-14 extension: resize to the next skip's size
@@ -736,17 +541,18 @@ class Engine(X3Path):
                 Ho, Wo = 2 * hh, 2 * ww
             if _COMMUTE_RESIZE:
                 # out_conv before the resize (see _COMMUTE_RESIZE): its backward reads u, not the 4x larger resized map
-                ul = ops.gemm_nt(u.view(-1, 256), self._w(P, r_ + "out_conv.weight", "lin"), self._f32(P, r_ + "out_conv.bias"))
-                path = ops.bilinear_fwd(ul.view(nb, hh, ww, 256), Ho, Wo, True)
-                up = None
+                ul = mm(u.view(nb * hh * ww, 256), r_ + "out_conv.weight", "lin", b_(r_ + "out_conv.bias"))
+                path = val(ops.bilinear_fwd(_f(ul).view(nb, hh, ww, 256), Ho, Wo, True))
                 del ul
+                src = ("u", u)
             else:
-                up = ops.bilinear_fwd(u, Ho, Wo, True)
-                path = ops.gemm_nt(up.view(-1, 256), self._w(P, r_ + "out_conv.weight", "lin"), self._f32(P, r_ + "out_conv.bias"))
-                path = path.view(nb, Ho, Wo, 256)
+                up = val(ops.bilinear_fwd(_f(u), Ho, Wo, True))
+                path = mm(up.view(nb * Ho * Wo, 256), r_ + "out_conv.weight", "lin", b_(r_ + "out_conv.bias")).view(nb, Ho, Wo, 256)
+                src = ("up", up)
             if save:
+                _drop_f(src[1])      # out_conv's weight gradient reads the planes, where there are any
                 fs.update(s_relu=s_relu, t2=t2, in_hw=(hh, ww))
-                fs.update(dict(u=u) if up is None else dict(up=up))
+                fs[src[0]] = src[1]
                 fus_saved[k] = fs
         if cfg["patch"] == 16:
             # models.py:70-72: Interpolate(scale_factor=2) -- the maps have 32 * (grid // 2 ...) = 16 * grid pixels per side, which is
@@ -758,7 +564,7 @@ class Engine(X3Path):
         # formed, and the backward of that layer -- weight gradient, data gradient, the algebraic head's reductions -- runs on
         # the quarter-size map
         lowres = _COMMUTE_RESIZE
-        feat = ops.bilinear_fwd(path, H, W, True) if not lowres else None
+        feat = val(ops.bilinear_fwd(_f(path), H, W, True)) if not lowres else None
         if save:
             S["fus"] = fus_saved
             S["rn_in"] = layers
@@ -768,18 +574,20 @@ class Engine(X3Path):
                 S["path"] = path
 
         # ---- heads (objectness_net.py:109-135)
-        outs = []
-        heads_saved = []
+        outs, heads_saved = [], []
+        M = B * H * W
+        low = tuple(path.shape[:3])
         for name, lay in (("center_field_prediction_head", self.center_layout), ("sdf_prediction_head", self.sdf_layout)):
             if name in skip:
                 outs.append(None)
                 continue
             idx = lay["conv_idx"]
+            final = _ACT[lay["final"]]
             if self._collapse(lay, save):
                 if lowres:
-                    out, cs = self._linear_head_forward_lowres(P, name, idx, path, H, W, _ACT[lay["final"]], save)
+                    out, cs = self._linear_head_forward_lowres(P, name, idx, _f(path), H, W, final, save)
                 else:
-                    out, cs = self._linear_head_forward(P, name, idx, feat, _ACT[lay["final"]])
+                    out, cs = self._linear_head_forward(P, name, idx, _f(feat), final)
                     cs["out"] = out
                 outs.append(out)
                 if save:
@@ -790,33 +598,21 @@ class Engine(X3Path):
             # (exact gradients from three pixel reductions over feat, _linear_head_backward); sin is not invertible from its value
             algebraic = save and not lay["relu"] and lay["final"] != "sine" and self.linear_head_backward == "algebraic"
             keep = save and not algebraic
+            hw, hb = (lambda j: f"{name}.{idx[j]}.weight"), (lambda j: b_(f"{name}.{idx[j]}.bias"))
             if lowres:
-                h1l = ops.gemm_nt(path.view(-1, 256), self._w(P, f"{name}.{idx[0]}.weight", "lin"), self._f32(P, f"{name}.{idx[0]}.bias"))
-                h1 = ops.bilinear_fwd(h1l.view(path.shape[0], path.shape[1], path.shape[2], -1), H, W, True, relu=lay["relu"]).view(B * H * W, -1)
+                h1l = mm(path.view(low[0] * low[1] * low[2], 256), hw(0), "lin", hb(0))
+                h1 = nx.head_resize(h1l, low, H, W, lay["relu"])
                 del h1l
             else:
-                h1 = ops.gemm_nt(feat.view(-1, 256), self._w(P, f"{name}.{idx[0]}.weight", "lin"), self._f32(P, f"{name}.{idx[0]}.bias"), act=act)
-            h2 = ops.gemm_nt(h1.view(B, H, W, 512), self._w(P, f"{name}.{idx[1]}.weight", "c3"), self._f32(P, f"{name}.{idx[1]}.bias"),
-                             conv=1, act=act)
-            w3, b3 = self._w(P, f"{name}.{idx[2]}.weight", "lin"), self._f32(P, f"{name}.{idx[2]}.bias")
-            w4 = self._f32(P, f"{name}.{idx[3]}.weight")
-            w4 = w4.reshape(w4.shape[0], -1)
-            b4 = self._f32(P, f"{name}.{idx[3]}.bias")
-            if _FUSE_HEAD_OUT and ops.gemm_nt(h2, w3, b3, act=act, query_rowreduce=True):
-                # the 1024 -> {1,2} output layer rides in the epilogue of the GEMM that produces its input (one read of
-                # h3 saved); without saved activations (inference) h3 is not written at all
-                h3, parts = ops.gemm_nt(h2, w3, b3, act=act, red_w=w4.contiguous(), no_store=not keep)
-                out = ops.head_out_finish(parts, b4, B, H, W, _ACT[lay["final"]])
-                # sin is not invertible from its value: the backward pass of the 'sine' variant gets the pre-activation
-                zpre = ops.head_out_finish(parts, b4, B, H, W, L.ACT_NONE) if (save and lay["final"] == "sine") else None
-                del parts
-            else:
-                h3 = ops.gemm_nt(h2, w3, b3, act=act)
-                out = ops.head_out_fwd(h3, w4, b4, B, H, W, _ACT[lay["final"]])
-                zpre = ops.head_out_fwd(h3, w4, b4, B, H, W, L.ACT_NONE) if (save and lay["final"] == "sine") else None
+                h1 = mm(feat.view(M, 256), hw(0), "lin", hb(0), act=act, want="p")
+            h2 = mm(h1.view(B, H, W, 512), hw(1), "c3", hb(1), conv=1, act=act, want="p")
+            w4 = b_(hw(3))
+            # sin is not invertible from its value: the backward pass of the 'sine' variant gets the pre-activation
+            out, h3, zpre = nx.head_tail(h2, hw(2), hb(2), w4.reshape(w4.shape[0], -1), hb(3), act, final, keep,
+                                         save and lay["final"] == "sine", B, H, W)
             outs.append(out)
             if algebraic:
-                heads_saved.append(dict(algebraic=True, act=_ACT[lay["final"]], out=out))
+                heads_saved.append(dict(algebraic=True, act=final, out=out))
             elif save:
                 heads_saved.append(dict(h1=h1, h2=h2, h3=h3, out=(zpre if zpre is not None else out)))
             del h1, h2, h3
@@ -946,9 +742,9 @@ class Engine(X3Path):
         stage_cb(name, wg) is called when a stage's gradients are complete or enqueued behind wg (the WgradStream of this pass):
         the data-parallel exchange launches its bucket there, a single-GPU step enqueues the stage's Adam update behind wg;
         join_at_stages: the caller reads the gradients inside stage_cb (so the weight-gradient stream is joined before each call)."""
-        cfg, dt = self.cfg, self.dt
-        if S.get("x3"):
-            return self.backward_x3(P, S, d_center, d_sdf, G, stage_cb, join_at_stages)
+        cfg = self.cfg
+        nx = S["numerics"](self, P)       # the numerics of the forward that saved S
+        mm, val = nx.mm, nx.val
         B, H, W, gh, gw = S["B"], S["H"], S["W"], S["gh"], S["gw"]
         D, heads, p = cfg["D"], cfg["heads"], cfg["patch"]
         g, Nt = gh * gw, gh * gw + 1
@@ -966,21 +762,16 @@ class Engine(X3Path):
                 stage_cb(name, wg)
             wg.stage_end()
 
-        def wgrad_lin(name, dy, x, bias_name=None, **kw):
-            wg.run(lambda: ops.gemm_tn(dy, x, dW=G[name].view(G[name].shape[0], -1), dbias=(G[bias_name] if bias_name else None), **kw), dy, x)
+        def wgrad_lin(name, dy, x, bias_name=None):
+            nx.wgrad(dy, x, G[name].view(G[name].shape[0], -1), (G[bias_name] if bias_name else None), wg=wg)
 
         def wgrad_c3(name, dy, x_nhwc, bias_name=None, conv=1):
             co = G[name].shape[0]
+            nx.wgrad(dy.view(-1, co), x_nhwc, None, (G[bias_name] if bias_name else None), conv=conv, wg=wg,
+                     then=lambda dwp: _unpack_conv3_grad(dwp, G[name]))
 
-            def launch():
-                dwp = ops.gemm_tn(dy.reshape(-1, co), x_nhwc, dbias=(G[bias_name] if bias_name else None), conv=conv)
-                _unpack_conv3_grad(dwp, G[name])
-            wg.run(launch, dy, x_nhwc)
-
-        # ---- heads
-        heads_bwd = self._heads_backward_lowres if S.get("path") is not None else self._heads_backward_fullres
-        dpath = heads_bwd(P, S, d_center, d_sdf, G, wgrad_lin, wgrad_c3)
-        cb("heads")
+        # ---- heads: the gradient of the last fusion block's output
+        dpath = nx.heads_backward(S, d_center, d_sdf, G, wgrad_lin, wgrad_c3, lambda: cb("heads"))
 
         # ---- refinenets + scratch convs
         sc = "backbone.scratch."
@@ -989,33 +780,31 @@ class Engine(X3Path):
             r_ = sc + f"refinenet{k}."
             fs = S["fus"][k]
             hh, ww = fs["in_hw"]
-            nb = dpath.shape[0]
+            nb, Hp, Wp = dpath.shape[0], dpath.shape[1], dpath.shape[2]
+            shp = (nb, hh, ww, 256)
             if "u" in fs:    # out_conv ran before the resize (_COMMUTE_RESIZE)
-                dul = ops.bilinear_bwd(dpath, hh, ww, True).view(-1, 256)
-                wgrad_lin(r_ + "out_conv.weight", dul, fs["u"].view(-1, 256), r_ + "out_conv.bias")
-                du = ops.gemm_nt(dul, self._w(P, r_ + "out_conv.weight", "lin_t"), None).view(nb, hh, ww, 256)
+                dul = val(ops.bilinear_bwd(_f(dpath), hh, ww, True)).view(nb * hh * ww, 256)
+                wgrad_lin(r_ + "out_conv.weight", dul, fs["u"].view(nb * hh * ww, 256), r_ + "out_conv.bias")
+                du = mm(dul, r_ + "out_conv.weight", "lin_t", None).view(*shp)
                 del dul
             else:
-                wgrad_lin(r_ + "out_conv.weight", dpath.reshape(-1, 256), fs["up"].view(-1, 256), r_ + "out_conv.bias")
-                dup = ops.gemm_nt(dpath.reshape(-1, 256), self._w(P, r_ + "out_conv.weight", "lin_t"), None)
-                du = ops.bilinear_bwd(dup.view(nb, dpath.shape[1], dpath.shape[2], 256), hh, ww, True)
+                dp2 = dpath.view(nb * Hp * Wp, 256)
+                wgrad_lin(r_ + "out_conv.weight", dp2, fs["up"].view(nb * Hp * Wp, 256), r_ + "out_conv.bias")
+                dup = _f(mm(dp2, r_ + "out_conv.weight", "lin_t", None))
+                du = val(ops.bilinear_bwd(dup.view(nb, Hp, Wp, 256), hh, ww, True))
                 del dup
             # RCU2: u = conv2(relu(conv1(relu(s)))) + s
             wgrad_c3(r_ + "resConfUnit2.conv2.weight", du, fs["t2"], r_ + "resConfUnit2.conv2.bias")
-            dt2 = ops.gemm_nt(du, self._w(P, r_ + "resConfUnit2.conv2.weight", "c3_d"), None, conv=1, aux=fs["t2"], mask_relu=True)
-            dt2 = dt2.view(nb, hh, ww, 256)
+            dt2 = mm(du, r_ + "resConfUnit2.conv2.weight", "c3_d", None, conv=1, mask=fs["t2"], want="p").view(*shp)
             wgrad_c3(r_ + "resConfUnit2.conv1.weight", dt2, fs["s_relu"], r_ + "resConfUnit2.conv1.bias")
-            ds = ops.gemm_nt(dt2, self._w(P, r_ + "resConfUnit2.conv1.weight", "c3_d"), None, conv=1, aux=fs["s_relu"], mask_relu=True,
-                             aux2=du).view(nb, hh, ww, 256)
+            ds = mm(dt2, r_ + "resConfUnit2.conv1.weight", "c3_d", None, conv=1, mask=fs["s_relu"], aux2=du, want="p").view(*shp)
             del dt2, du
             if "t1" in fs:
                 # s = path_prev + RCU1(x1)
                 wgrad_c3(r_ + "resConfUnit1.conv2.weight", ds, fs["t1"], r_ + "resConfUnit1.conv2.bias")
-                dt1 = ops.gemm_nt(ds, self._w(P, r_ + "resConfUnit1.conv2.weight", "c3_d"), None, conv=1, aux=fs["t1"], mask_relu=True)
-                dt1 = dt1.view(nb, hh, ww, 256)
+                dt1 = mm(ds, r_ + "resConfUnit1.conv2.weight", "c3_d", None, conv=1, mask=fs["t1"], want="p").view(*shp)
                 wgrad_c3(r_ + "resConfUnit1.conv1.weight", dt1, fs["x1_relu"], r_ + "resConfUnit1.conv1.bias")
-                dx1 = ops.gemm_nt(dt1, self._w(P, r_ + "resConfUnit1.conv1.weight", "c3_d"), None, conv=1, aux=fs["x1_relu"],
-                                  mask_relu=True, aux2=ds).view(nb, hh, ww, 256)
+                dx1 = mm(dt1, r_ + "resConfUnit1.conv1.weight", "c3_d", None, conv=1, mask=fs["x1_relu"], aux2=ds, want="p").view(*shp)
                 del dt1
                 d_rn[k] = dx1
                 dpath = ds  # gradient of the previous (coarser) path
@@ -1027,12 +816,14 @@ class Engine(X3Path):
         # ---- layerK_rn + reassemble + readout; token gradients collected per hook
         pp = "backbone.pretrained."
         Fs = cfg["features"]
-        d_hook = [None] * 4  # (d_rpre [B*g, D], sB) applied to the token gradient when the block is reached
+        d_hook = [None] * 4  # (d_rpre [B*g, D], sB [B, D], readout weight's name) applied to the token gradient when the block is reached
         for k in range(4):
             lay_in = S["rn_in"][k]
             dr = d_rn.pop(k + 1)
             wgrad_c3(sc + f"layer{k + 1}_rn.weight", dr, lay_in, None)
-            dl = ops.gemm_nt(dr, self._w(P, sc + f"layer{k + 1}_rn.weight", "c3_d"), None, conv=1)
+            # dl: gradient of the reassembled map; f32 where a non-GEMM kernel (pixel shuffle, zero stuffing) or the stride-2
+            # weight gradient reads it
+            dl = mm(dr, sc + f"layer{k + 1}_rn.weight", "c3_d", None, conv=1, want=("p" if k == 2 else "f"))
             del dr
             a = pp + f"act_postprocess{k + 1}."
             F_ = Fs[k]
@@ -1040,51 +831,38 @@ class Engine(X3Path):
             f = rs["f"]
             if k in (0, 1):
                 s = 4 if k == 0 else 2
-                dyu = ops.pixel_shuffle(dl.view(B, gh * s, gw * s, F_), B, gh, gw, s, F_, inverse=True)  # [B*g, s*s*F]
+                dyu = val(ops.pixel_shuffle(_f(dl).view(B, gh * s, gw * s, F_), B, gh, gw, s, F_, inverse=True))  # [B*g, s*s*F]
                 brep = torch.empty(s * s * F_, dtype=torch.float32, device=dev)
-                dwp = ops.gemm_tn(dyu, f, dbias=brep)  # [(i,j,co)][ci]
+                dwp = nx.wgrad(dyu, f.view(B * g, F_), None, brep)  # [(i,j,co)][ci]
                 gw_ = G[a + "4.weight"]  # [ci, co, s, s]
                 ops.permute4(dwp, gw_, (F_, F_, s, s), (1, F_, s * F_ * F_, F_ * F_))
                 ops.segsum(brep, 1, s * s, F_, 0, F_, out=G[a + "4.bias"].view(1, F_))
-                df = ops.gemm_nt(dyu, self._w(P, a + "4.weight", "ct_d"), None)
+                df = mm(dyu, a + "4.weight", "ct_d", None, want="p")
                 del dyu
             elif k == 2:
-                df = dl.view(-1, F_)
+                df = dl.view(B * g, F_)
             else:
                 ho, wo = (gh - 1) // 2 + 1, (gw - 1) // 2 + 1
                 wgrad_c3(a + "4.weight", dl, f.view(B, gh, gw, F_), a + "4.bias", conv=2)
-                stuffed = ops.zero_stuff2(dl.view(B, ho, wo, F_), gh, gw)
-                df = ops.gemm_nt(stuffed, self._w(P, a + "4.weight", "c3_d"), None, conv=1)
+                stuffed = val(ops.zero_stuff2(_f(dl).view(B, ho, wo, F_), gh, gw))
+                df = mm(stuffed, a + "4.weight", "c3_d", None, conv=1, want="p").view(B * g, F_)
                 del stuffed
             del dl
             wgrad_lin(a + "3.weight", df, rs["r"], a + "3.bias")
-            d_rpre = ops.gemm_nt(df, self._w(P, a + "3.weight", "lin_t"), None, aux=rs["rpre"], mask_dgelu=True)  # [B*g, D]
+            d_rpre = mm(df, a + "3.weight", "lin_t", None, dgelu=rs["rpre"], want="p")  # [B*g, D]
             del df
             tok = S["acts"][k]
-            gfull = G[a + "0.project.0.weight"]  # [D, 2D]
-            ops.gemm_tn(d_rpre, tok, dW=gfull[:, :D], x_remap=(g, Nt, 1), M=B * g)
-            sB32 = ops.segsum(d_rpre, B, g, D, g * D, D)  # [B, D] f32: sum over patches
+            wname = a + "0.project.0.weight"
+            gfull = G[wname]  # [D, 2D]: token half | class-token half
+            nx.readout_wgrad(d_rpre, rs, tok, gfull[:, :D], B, g, Nt)
+            sB32 = ops.segsum(_f(d_rpre), B, g, D, g * D, D)  # [B, D] f32: sum over patches
             ops.segsum(sB32, 1, B, D, 0, D, out=G[a + "0.project.0.bias"].view(1, D))
-            sBt = sB32 if dt == torch.float32 else ops.cast(sB32, dt)
-            ops.gemm_tn(sBt, tok, dW=gfull[:, D:], M=B, ldx=Nt * D)
-            d_hook[k] = (d_rpre, sBt, a)
+            sB = nx.to_dt(sB32)
+            ops.gemm_tn(sB, tok, dW=gfull[:, D:], M=B, ldx=Nt * D)   # class-token half: B rows (tiny)
+            d_hook[k] = (d_rpre, sB, wname)
             S["re"][k] = None
 
         cb("reassemble")
-
-        def add_hook_grad(k, dx):
-            d_rpre, sBt, a = d_hook[k]
-            wname = a + "0.project.0.weight"
-            w = P[wname].detach()
-            wa_t = self.cache.get((wname, "lin_t_a", dt), P[wname], lambda: _pack_linear_t(w[:, :D], dt))
-            wb_t = self.cache.get((wname, "lin_t_b", dt), P[wname], lambda: _pack_linear_t(w[:, D:], dt))
-            if dx is None:
-                dx = torch.zeros((B * Nt, D), dtype=dt, device=dev)
-            ops.gemm_nt(d_rpre, wa_t, None, out=dx, aux=dx, c_remap=(g, Nt, 1))
-            cls_rows = dx.view(B, Nt * D)[:, :D]  # token 0 of every image: row stride Nt*D
-            ops.gemm_nt(sBt, wb_t, None, out=cls_rows, aux=cls_rows)
-            d_hook[k] = None
-            return dx
 
         # ---- transformer blocks
         m = "backbone.pretrained.model."
@@ -1092,23 +870,27 @@ class Engine(X3Path):
         hooks = cfg["hooks"]
         for i in range(max(hooks), -1, -1):
             if i in hooks:
-                dx = add_hook_grad(hooks.index(i), dx)
+                k = hooks.index(i)
+                dx = nx.hook_grad(*d_hook[k], dx, B, g, Nt, D)
+                d_hook[k] = None
             b = m + f"blocks.{i}."
             bs = S["blocks"][i]
-            wgrad_lin(b + "mlp.fc2.weight", dx, bs["h"], b + "mlp.fc2.bias")
-            dhp = ops.gemm_nt(dx, self._w(P, b + "mlp.fc2.weight", "lin_t"), None, aux=bs["hpre"], mask_dgelu=True)
+            dxx = val(dx)
+            wgrad_lin(b + "mlp.fc2.weight", dxx, bs["h"], b + "mlp.fc2.bias")
+            dhp = mm(dxx, b + "mlp.fc2.weight", "lin_t", None, dgelu=bs["hpre"], want="p")
             wgrad_lin(b + "mlp.fc1.weight", dhp, bs["ln2"], b + "mlp.fc1.bias")
-            dln2 = ops.gemm_nt(dhp, self._w(P, b + "mlp.fc1.weight", "lin_t"), None)
-            del dhp
+            dln2 = _f(mm(dhp, b + "mlp.fc1.weight", "lin_t", None))
+            del dhp, dxx
             dx1 = ops.layernorm_bwd(dln2, bs["x1"], self._f32(P, b + "norm2.weight"), bs["mean2"], bs["rstd2"],
                                     G[b + "norm2.weight"], G[b + "norm2.bias"], dres=dx, params_via=ln_via)
             del dln2
-            wgrad_lin(b + "attn.proj.weight", dx1, bs["att"], b + "attn.proj.bias")
-            datt = ops.gemm_nt(dx1, self._w(P, b + "attn.proj.weight", "lin_t"), None)
-            dqkv = ops.attention_bwd(bs["qkv"], bs["att"], datt, bs["lse"], B, Nt, heads)
-            del datt
+            dx1x = val(dx1)
+            wgrad_lin(b + "attn.proj.weight", dx1x, bs["att"], b + "attn.proj.bias")
+            datt = _f(mm(dx1x, b + "attn.proj.weight", "lin_t", None))
+            dqkv = val(ops.attention_bwd(bs["qkv"], _f(bs["att"]), datt, bs["lse"], B, Nt, heads))
+            del datt, dx1x
             wgrad_lin(b + "attn.qkv.weight", dqkv, bs["ln1"], b + "attn.qkv.bias")
-            dln1 = ops.gemm_nt(dqkv, self._w(P, b + "attn.qkv.weight", "lin_t"), None)
+            dln1 = _f(mm(dqkv, b + "attn.qkv.weight", "lin_t", None))
             del dqkv
             dx = ops.layernorm_bwd(dln1, bs["x"], self._f32(P, b + "norm1.weight"), bs["mean1"], bs["rstd1"],
                                    G[b + "norm1.weight"], G[b + "norm1.bias"], dres=dx1, params_via=ln_via)
@@ -1130,10 +912,9 @@ class Engine(X3Path):
         gwp = G[m + "patch_embed.proj.weight"].view(D, K)
         patches = S["patches"]
         if patches.shape[1] == K:
-            ops.gemm_tn(dx, patches, dW=gwp, dbias=G[m + "patch_embed.proj.bias"], dy_remap=(g, Nt, 1), M=B * g)
+            nx.patch_wgrad(dx, patches, gwp, G[m + "patch_embed.proj.bias"], B, g, Nt)
         else:
-            tmp = ops.gemm_tn(dx, patches, dbias=G[m + "patch_embed.proj.bias"], dy_remap=(g, Nt, 1), M=B * g)
-            gwp.copy_(tmp[:, :K])
+            gwp.copy_(nx.patch_wgrad(dx, patches, None, G[m + "patch_embed.proj.bias"], B, g, Nt)[:, :K])
         cb("embed")
         wg.join()
         S.clear()
