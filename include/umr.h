@@ -492,6 +492,35 @@ int umr_label_synthesis_cropped(const uint8_t* mask, const float* center_xy, con
                                 float* saliency, float* sdf, void* workspace, int64_t workspace_bytes, int B, int H, int W,
                                 int use_bg_sdf, umr_stream_t stream);
 
+/* ---- the existence classifier's training item (datasets.py:285-349 after file decoding) ---------------------------------
+ * Items of a batch differ in size: both entry points take a RAGGED batch, a device table of B umr_ragged_src entries the
+ * host uploads in one copy, and launch once for the whole batch.
+ * bg_square (background branch, :304-313): per item, on its mask `u8` [H,W] (non-zero = object), the 3x3 chamfer transform
+ *   of `mask == 0` with a ZERO border (what the reference's ten rings of zero padding amount to: the image edge is an
+ *   obstacle), the first maximum in raster order of the float32 field (fixed * 2^-16 rounded to float32, ties decided after
+ *   the conversion), r = that maximum, and the box x1 = int(x - r), y1 = int(y - r), x2 = int(x + r), y2 = int(y + r)
+ *   (float64 arithmetic, truncation toward zero, clamped to the image as the slice :316 clamps).  out: int32 [B,5] =
+ *   (x1, y1, x2, y2, ok), ok = 0 for an empty box (x2 <= x1 or y2 <= y1: the reference's resize raises and the item falls
+ *   through to the foreground branch, :324-325).  An entry that breaks the limits below on the device comes back as
+ *   (-1,-1,-1,-1,0).  max_w / max_pixels: the widest row and the largest H*W in the table (max_w > 4096: UMR_ERR_UNSUPPORTED);
+ *   workspace >= bg_square_workspace(B, max_pixels): one int32 field per item, written and read once.
+ * crop_resize_ragged (:316-319 and :335-346): per item the box [x1,y1,x2,y2) of its `f32` source [C,H,W] -> dst [B,C,Ho,Wo],
+ *   crop_resize_batch's bilinear arithmetic.  With mask_sum != NULL one more channel: `u8` [H,W] read as u8 / 255 in f32
+ *   (to_tensor) before interpolation -> mask_out [B,Ho,Wo], and its sum over the Ho*Wo resized values -> mask_sum [B] (the
+ *   label is mask_sum > 1, :343).  An entry with u8 == NULL (a background-branch item) gets a zero mask and sum 0.  One
+ *   workgroup per (item, channel plane); the sum adds fixed per-thread strides, then a fixed tree: bitwise reproducible,
+ *   no atomics.  Boxes are clamped to the source; an empty box yields zeros. */
+typedef struct umr_ragged_src {
+    const float* f32;     /* [C,H,W] f32 planes (crop_resize_ragged) */
+    const uint8_t* u8;    /* [H,W] u8 mask (bg_square; crop_resize_ragged: optional extra channel) */
+    int32_t H, W;
+} umr_ragged_src;
+int64_t umr_bg_square_workspace(int B, int64_t max_pixels);
+int umr_bg_square(const umr_ragged_src* items, int32_t* out, void* workspace, int64_t workspace_bytes, int B, int max_w,
+                  int64_t max_pixels, umr_stream_t stream);
+int umr_crop_resize_ragged(const umr_ragged_src* items, const int32_t* boxes, float* dst, float* mask_out, float* mask_sum,
+                           int B, int C, int Ho, int Wo, umr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

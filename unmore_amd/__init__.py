@@ -4,3 +4,4 @@ from .trainer import TrainStep  # noqa: F401
 from .loss import objectness_loss  # noqa: F401
 from .binary_classifier import Binary_Classifier  # noqa: F401
 from .classifier_trainer import ClassifierTrainStep  # noqa: F401
+from .labels import synthesize_classifier_items  # noqa: F401

@@ -50,6 +50,10 @@ class BnBwdDesc(ctypes.Structure):   # umr_bn_bwd_desc
                 ("rows_per_batch", _i64), ("pool_scale", ctypes.c_float), ("M", _i32), ("C", _i32), ("nbranch", _i32), ("dtype", _i32)]
 
 
+class RaggedSrc(ctypes.Structure):   # umr_ragged_src
+    _fields_ = [("f32", _vp), ("u8", _vp), ("H", _i32), ("W", _i32)]
+
+
 class PermEntry(ctypes.Structure):   # umr_perm_entry
     _fields_ = [("src", _vp), ("dst", _vp), ("d", _i32 * 4), ("sstride", _i64 * 4), ("soff", _i64), ("dtype_in", _i32), ("dtype_out", _i32),
                 ("blk_start", _i64), ("e", _i32 * 4), ("ord", _i32 * 4), ("rowlen", _i64)]
@@ -83,6 +87,9 @@ _SIGS = {
     "umr_crop_resize_batch": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "umr_distance_transform_workspace": [_i32, _i32, _i32],
     "umr_distance_transform": [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp],
+    "umr_bg_square_workspace": [_i32, _i64],
+    "umr_bg_square": [_vp, _vp, _vp, _i64, _i32, _i32, _i64, _vp],
+    "umr_crop_resize_ragged": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
     "umr_im2col_nchw": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
     "umr_maxpool3x3s2": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
     "umr_bn_fold": [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
@@ -182,7 +189,7 @@ def lib():
         for fn in ("umr_gemm_tn_workspace", "umr_layernorm_bwd_workspace", "umr_head_out_bwd_workspace", "umr_loss_workspace",
                    "umr_linear_head_bwd_weight_workspace", "umr_linear_head_shift9_workspace", "umr_label_synthesis_workspace", "umr_attention_bwd_workspace",
                    "umr_distance_transform_workspace", "umr_gemm_nt_workspace", "umr_gemm_nt_x3_workspace", "umr_nms_workspace",
-                   "umr_bn_train_workspace"):
+                   "umr_bn_train_workspace", "umr_bg_square_workspace"):
             getattr(_lib, fn).restype = ctypes.c_int64
     return _lib
 

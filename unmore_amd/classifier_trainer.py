@@ -308,6 +308,30 @@ class ClassifierTrainStep(AdamState):
                 return outs[0].clone()
         return self._body(images, labels)[0]
 
+    def evaluate(self, batches):
+        """The reference's evaluate_classification (train_objectness_net.py:703-743) without its image dump: `batches` yields
+        (images [B, 3, H, W], class_labels [B, 1]); the model runs in eval() mode under no_grad (Binary_Classifier.forward: running
+        statistics folded into the convolutions), hits += ((pred > 0.5) == label).sum() accumulates on the device and is read
+        once at the end.  Returns (hits, total); accuracy = hits / total is what the reference logs under the iteration.
+        The model goes back into the mode it was in, also when a batch raises.  Nothing the step owns is touched: parameters,
+        running statistics, Adam state, `iter` and the captured step graphs are as before."""
+        was_training = self.net.training
+        self.net.eval()
+        hits, total = None, 0
+        try:
+            with torch.no_grad():
+                for images, class_labels in batches:
+                    if not (images.is_cuda and class_labels.is_cuda):
+                        raise RuntimeError("unmore_amd.ClassifierTrainStep runs on the MI355X only (no CPU fallback); move images and labels "
+                                           "to the GPU")
+                    pred = self.net(images=images)                                                  # :716
+                    n = ((pred > 0.5).to(class_labels.dtype) == class_labels.reshape(pred.shape)).sum()   # :717-719
+                    hits = n if hits is None else hits + n
+                    total += pred.shape[0]                                                          # :719
+        finally:
+            self.net.train(was_training)                                                            # :741
+        return (int(hits.item()) if hits is not None else 0), total
+
     def grads(self):
         """{parameter name: gradient view} of the last step (views into the flat gradient buffer)"""
         return dict(self.G)

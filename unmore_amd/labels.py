@@ -161,3 +161,117 @@ def synthesize_training_items(images, masks, image_size, scale=(0.08, 1.0), use_
         cf[e] = 0; sal[e] = 0; sdf[e] = 0; inst[e] = 0; centers[e] = 0
     labels = {"center_field": cf, "saliency_mask": sal, "instance_mask": inst, "object_center": centers, "sdf": sdf}
     return img_s, labels, params
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# The existence classifier's training item (datasets.py:285-349, ImageNet_votecut_labeled_classifier_Dataset.__getitem__)
+# ---------------------------------------------------------------------------------------------------------------------
+import ctypes
+import random
+
+import numpy as np
+
+_RAGGED_INTS = ctypes.sizeof(L.RaggedSrc) // 4     # a table entry in int32 units (two pointers, H, W)
+
+
+def _ragged_upload(f32s, u8s, shapes, extra, dev):
+    """One host-to-device copy: the umr_ragged_src table of a ragged batch followed by `extra` (int32 arrays).  Returns the
+    device buffer (int32) and the element offsets of the extras in it."""
+    n = len(shapes)
+    tab = (L.RaggedSrc * n)()
+    for k, (h, w) in enumerate(shapes):
+        tab[k].f32 = f32s[k].data_ptr() if f32s[k] is not None else None
+        tab[k].u8 = u8s[k].data_ptr() if u8s[k] is not None else None
+        tab[k].H, tab[k].W = h, w
+    parts = [np.frombuffer(tab, dtype=np.int32)] + [np.asarray(e, dtype=np.int32).reshape(-1) for e in extra]
+    offs = np.cumsum([0] + [p.size for p in parts])[1:-1].tolist()
+    return torch.from_numpy(np.concatenate(parts)).to(dev), offs
+
+
+def background_squares(full_masks):
+    """datasets.py:304-313 for a ragged batch: full_masks is a list of [h,w] u8 tensors on the GPU (non-zero = object).  Returns
+    int32 [B,5] = (x1, y1, x2, y2, ok) on the device: the largest background square around the first float32 maximum of the
+    zero-border 3x3 chamfer transform of `mask == 0`; ok = 0 for an empty box.  One launch, no synchronisation."""
+    if not all(m.is_cuda for m in full_masks):
+        raise RuntimeError("unmore_amd.background_squares runs on the MI355X only (no CPU fallback); move the masks to the GPU")
+    if not full_masks or any(m.dim() != 2 or m.dtype != torch.uint8 for m in full_masks):
+        raise ValueError("background_squares: a non-empty list of [h,w] uint8 masks expected")
+    dev = full_masks[0].device
+    ms = [m.contiguous() for m in full_masks]
+    shapes = [(int(m.shape[0]), int(m.shape[1])) for m in ms]
+    n = len(ms)
+    tab, _ = _ragged_upload([None] * n, ms, shapes, [], dev)
+    max_w, max_px = max(w for _, w in shapes), max(h * w for h, w in shapes)
+    nbytes = L.lib().umr_bg_square_workspace(n, max_px)
+    ws = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+    out5 = torch.empty((n, 5), dtype=torch.int32, device=dev)
+    L.check(L.lib().umr_bg_square(_p(tab), _p(out5), _p(ws), nbytes, n, max_w, max_px, _stream()), "umr_bg_square")
+    return out5
+
+
+def synthesize_classifier_items(images, top1_masks, full_masks, image_size, coins=None, params=None, generator=None):
+    """A batch of the existence classifier's training items (datasets.py:285-349 after the cv2.imread calls) on the device.
+    images: list of [3,h,w] f32 tensors in [0,1] on the GPU (sizes differ between items); top1_masks / full_masks: lists of
+    [h,w] u8 tensors holding the raw PNG values of the top-1 single-component mask (`mask_folder`) and of the full VoteCut
+    mask (`full_mask_folder`).  A mask stored transposed is rotated by the caller (torch.rot90(mask, -1), :300-302).
+    coins: list of bools, True = try the background branch (tests); None = `random.random() < 0.5` per item in item order
+    (Python's `random`, :286-289, as a single-worker loader draws them).
+    params: list of (top, left, h, w) or None per item (tests); None = `random_resized_crop_params(h, w, ratio=(3/4, 4/3),
+    generator=generator)` (RandomResizedCrop's defaults, :338) for exactly the items that take the foreground branch, in
+    item order -- items that succeed on the background branch draw nothing.
+    Background branch (:304-321): the largest background square of the full mask (zero-border 3x3 chamfer transform, first
+    float32 maximum, box = int(centre -/+ radius)), cropped from the image and resized bilinearly; label 0.  An empty box
+    (a mask without background, or a maximum in row / column 0) falls through to the foreground branch (:324-325): there
+    torchvision's resize raises on the empty crop -- read from the code, not executed (neither cv2 nor torchvision was
+    available where this was written).
+    Foreground branch (:335-346): image and top-1 mask / 255 cropped by the RandomResizedCrop box and resized bilinearly;
+    label 1 if the resized mask sums to more than 1.
+    Returns images [B,3,S,S] f32, class_labels [B,1] f32 and info = {'branch': int32 [B] (0 background / 1 foreground),
+    'boxes': int32 [B,4] (x1, y1, x2, y2) in source pixels, 'mask_sum': f32 [B] (0 for background items)}, all on the device.
+    The call reads the background pass's [B,5] box table back once; that is its only synchronisation."""
+    B, S = len(images), int(image_size)
+    if not (B > 0 and len(top1_masks) == B and len(full_masks) == B):
+        raise ValueError("synthesize_classifier_items: images, top1_masks and full_masks are lists of the same, non-zero length")
+    if not all(t.is_cuda for t in list(images) + list(top1_masks) + list(full_masks)):
+        raise RuntimeError("unmore_amd.synthesize_classifier_items runs on the MI355X only (no CPU fallback); move images and masks to the GPU")
+    dev = images[0].device
+    imgs = [im.float().contiguous() for im in images]
+    shapes = [(int(im.shape[1]), int(im.shape[2])) for im in imgs]
+    for im, m1, mf, hw in zip(imgs, top1_masks, full_masks, shapes):
+        if im.dim() != 3 or im.shape[0] != 3 or tuple(m1.shape) != hw or tuple(mf.shape) != hw or m1.dtype != torch.uint8 or mf.dtype != torch.uint8:
+            raise ValueError("synthesize_classifier_items: items are ([3,h,w] float image, [h,w] uint8 top-1 mask, [h,w] uint8 full mask)")
+    if coins is None:
+        coins = [random.random() < 0.5 for _ in range(B)]                                             # :286-289
+    if len(coins) != B or (params is not None and len(params) != B):
+        raise ValueError("synthesize_classifier_items: coins / params hold one entry per item")
+    # ---- background pass over the items whose coin says so
+    bg = [b for b in range(B) if coins[b]]
+    bg_box = {}
+    if bg:
+        out5 = background_squares([full_masks[b] for b in bg])
+        for b, row in zip(bg, out5.cpu().tolist()):                                                   # the call's one synchronisation
+            if row[4]:
+                bg_box[b] = row[:4]
+    # ---- boxes: background squares where they exist, RandomResizedCrop boxes for everything else, drawn in item order
+    branch, boxes = [], []
+    for b, (h, w) in enumerate(shapes):
+        if b in bg_box:
+            branch.append(0)
+            boxes.append(bg_box[b])
+            continue
+        p = params[b] if params is not None and params[b] is not None else \
+            random_resized_crop_params(h, w, ratio=(3.0 / 4.0, 4.0 / 3.0), generator=generator)      # :338
+        top, left, ph, pw = (int(v) for v in p)
+        branch.append(1)
+        boxes.append([left, top, left + pw, top + ph])
+    # ---- one crop + resize launch for the whole batch; the top-1 mask rides along on foreground items only
+    m1s = [top1_masks[b].contiguous() if branch[b] else None for b in range(B)]
+    tab, (o_box, o_br) = _ragged_upload(imgs, m1s, shapes, [boxes, branch], dev)
+    out = torch.empty((B, 3, S, S), dtype=torch.float32, device=dev)
+    m_out = torch.empty((B, S, S), dtype=torch.float32, device=dev)
+    m_sum = torch.empty(B, dtype=torch.float32, device=dev)
+    L.check(L.lib().umr_crop_resize_ragged(_p(tab), _p(tab[o_box:]), _p(out), _p(m_out), _p(m_sum), B, 3, S, S, _stream()),
+            "umr_crop_resize_ragged")
+    class_labels = (m_sum > 1).to(torch.float32).view(B, 1)                                           # :343-346; background items sum to 0
+    info = {"branch": tab[o_br:o_br + B], "boxes": tab[o_box:o_br].view(B, 4), "mask_sum": m_sum}
+    return out, class_labels, info
