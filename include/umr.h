@@ -366,6 +366,22 @@ int umr_mask_paste_stats(const float* sdf_maps, const float* center_fields, cons
                          int32_t* stats, float* maxima, umr_stream_t stream);
 int umr_mask_paste(const float* sdf_maps, const float* center_fields, const int32_t* boxes, const int64_t* select, int K, int S, int H, int W,
                    uint8_t* masks, umr_stream_t stream);
+/* COCO run-length strings of binary masks (pycocotools' maskApi.c format; the `segmentation` of the records object_scoring.py:166-170,
+ * 257-272 writes): pixels in column-major order (j = x*H + y), counts = lengths of the alternating runs starting with zeros, run i
+ * written as counts[i] - (i > 2 ? counts[i-2] : 0) in 5-bit groups (low first, 0x20 = another follows, character = group + 48).
+ * rle_encode: masks [K,H,W] u8 on the device (0 = clear, anything else = set).  mask_paste_rle: the pasted union masks of the K selected
+ *   proposals -- the arguments and, bit for bit, the masks of umr_mask_paste -- encoded from the two crop masks in LDS over the box's
+ *   columns only; the masks themselves are never written.
+ * Both run as two passes over caller-owned buffers (the library allocates nothing, there is no workspace):
+ *   measure: chars == NULL; sizes[k] = {number of runs, number of characters} (int64 [K][2]; the worst case is H*W + 1 runs).
+ *   write:   chars != NULL; mask k's characters go to chars[offsets[k] ...) (int64 [K], the caller's prefix sum of the measured
+ *            character counts; no terminator); nothing is stored at or beyond chars_capacity.  sizes is not touched.
+ * The same input gives the same bytes on every run.  H*W < 2^31; rle_encode with W > 1: H <= 32764 (UMR_ERR_UNSUPPORTED beyond);
+ * mask_paste_rle: S <= 256. */
+int umr_rle_encode(const uint8_t* masks, int K, int H, int W, int64_t* sizes, const int64_t* offsets, uint8_t* chars, int64_t chars_capacity,
+                   umr_stream_t stream);
+int umr_mask_paste_rle(const float* sdf_maps, const float* center_fields, const int32_t* boxes, const int64_t* select, int K, int S, int H, int W,
+                       int64_t* sizes, const int64_t* offsets, uint8_t* chars, int64_t chars_capacity, umr_stream_t stream);
 /* mask_components: 8-connected components of every map's union mask (sigmoid(sdf) > 0.5 | ||center|| > 0.5) in scipy.ndimage.label's
  * order (by first pixel in raster order) -- object_reasoning.py:206-257, the --analyze_cc branch of center_reasoning (README.md:176).
  * counts[b] = the number of components of map b; boxes[b][i] = [x1, y1, x2, y2) of component i for i < min(counts[b], max_components),

@@ -5,3 +5,4 @@ from .loss import objectness_loss  # noqa: F401
 from .binary_classifier import Binary_Classifier  # noqa: F401
 from .classifier_trainer import ClassifierTrainStep  # noqa: F401
 from .labels import synthesize_classifier_items  # noqa: F401
+from . import rle  # noqa: F401
