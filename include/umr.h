@@ -382,6 +382,33 @@ int umr_rle_encode(const uint8_t* masks, int K, int H, int W, int64_t* sizes, co
                    umr_stream_t stream);
 int umr_mask_paste_rle(const float* sdf_maps, const float* center_fields, const int32_t* boxes, const int64_t* select, int K, int S, int H, int W,
                        int64_t* sizes, const int64_t* offsets, uint8_t* chars, int64_t chars_capacity, umr_stream_t stream);
+/* rle_decode: the other direction, K strings -> G masks, parsed on the device (utils/preprocess_votecut.py:71-94 and
+ * utils/vis_votecut.py:57-79 without pycocotools / cv2).  chars: the characters of the K strings packed in one buffer, string k =
+ * chars[char_offsets[k] .. char_offsets[k+1]) (int64 [K+1], char_offsets[K] == total_chars).  Output g is a row-major [H,W] u8 mask at
+ * out + out_desc[g][2] with (H, W) = out_desc[g][0..1] (int64 [G][3]; ragged: every output has its own size and byte offset), made from
+ * the records group_start[g] .. group_start[g+1]-1 (int32 [G+1], ascending, group_start[0] == 0, group_start[G] == K), which all have
+ * that size.  A set pixel is written as `value`, a clear one as 0; an empty group gives an all-zero mask.  max_pixels: the largest
+ * H*W in out_desc (< 2^31).
+ *   mode 0: the OR of the group's records.
+ *   mode 1: the largest 4-connected component of the group's one record: largest area, ties to the
+ *           component whose first pixel in raster order comes first (np.argmax over cv2.connectedComponentsWithStats' areas).
+ *           info[g] = (number of components, area of the kept one) (int32 [G][2]; (0, 0) for an empty mask).  seg_offsets: int64 [G+1],
+ *           the caller's prefix sum of nchars/2 + 1 + W per record (an upper bound of the column-split runs of ones, known without
+ *           parsing); total_segments = seg_offsets[G].  mode 0 ignores seg_offsets, total_segments and info.  K != G is
+ *           UMR_ERR_INVALID.  With K == G, a group_start that still gives a group two records or none is seen on the device only:
+ *           every such group gets an all-zero mask and status 8 on each of its records (a group without records has none to mark:
+ *           one of the others then holds two).
+ * status[k] (int32 [K]): 0 = ok, else a bit set: 1 a character outside the format or a string that stops inside a number, 2 a number
+ * of more than 7 characters or a count outside [0, H*W], 4 counts that do not sum to H*W, 8 a table entry out of range.  A record
+ * with non-zero status is never labelled and contributes nothing (mode 1: an all-zero mask).  Nothing is stored outside
+ * [out, out + out_bytes), status, info and the workspace, whatever the strings say.  The caller owns every buffer; workspace >=
+ * rle_decode_workspace(K, total_chars, total_segments, mode) bytes, 8-byte aligned.  Two launches, no synchronisation; the same input
+ * gives the same bytes on every run. */
+int64_t umr_rle_decode_workspace(int K, int64_t total_chars, int64_t total_segments, int mode);
+int umr_rle_decode(const uint8_t* chars, const int64_t* char_offsets, int K, int64_t total_chars, const int64_t* out_desc,
+                   const int32_t* group_start, const int64_t* seg_offsets, int G, int64_t max_pixels, int64_t total_segments, uint8_t* out,
+                   int64_t out_bytes, int value, int mode, int32_t* status, int32_t* info, void* workspace, int64_t workspace_bytes,
+                   umr_stream_t stream);
 /* mask_components: 8-connected components of every map's union mask (sigmoid(sdf) > 0.5 | ||center|| > 0.5) in scipy.ndimage.label's
  * order (by first pixel in raster order) -- object_reasoning.py:206-257, the --analyze_cc branch of center_reasoning (README.md:176).
  * counts[b] = the number of components of map b; boxes[b][i] = [x1, y1, x2, y2) of component i for i < min(counts[b], max_components),

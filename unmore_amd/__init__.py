@@ -6,3 +6,5 @@ from .binary_classifier import Binary_Classifier  # noqa: F401
 from .classifier_trainer import ClassifierTrainStep  # noqa: F401
 from .labels import synthesize_classifier_items  # noqa: F401
 from . import rle  # noqa: F401
+from . import votecut  # noqa: F401
+from .votecut import VoteCutAnnotations  # noqa: F401

@@ -9,6 +9,8 @@ has 0x20 set; every group is the character chr(c + 48).  A record is {"size": [H
 `encode` / `encode_pasted` run on the device (csrc/rle.hip): a measure pass, one small read of the sizes, a write pass into a packed
 buffer, one read of the characters -- nothing image-sized crosses to the host.  The *_numpy functions restate the format on the CPU:
 what the tests compare the kernels against and what a host without a GPU reads the file back with."""
+import ctypes
+
 import numpy as np
 
 
@@ -150,3 +152,145 @@ def encode_pasted(sdf, center, int_boxes, select, H, W):
         L.check(L.lib().umr_mask_paste_rle(_p(sdf), _p(center), _p(int_boxes), _p(select), K, S, H, W, _p(sizes), _p(offsets), _p(chars), cap,
                                            _stream()), "umr_mask_paste_rle")
     return _two_pass(launch, K, H, W, sdf.device)
+
+
+# ---------------------------------------------------------------------------------------------------------------- strings -> masks
+_STATUS_BITS = ((1, "a character outside the format or a string that stops inside a number"),
+                (2, "a number of more than 7 characters or a count outside [0, H*W]"),
+                (4, "counts that do not sum to H*W"),
+                (8, "a table entry out of range"))
+
+
+def _as_record(rec, k, what):
+    """a segmentation -> (H, W, counts as bytes); uncompressed count lists are converted with counts_to_string"""
+    if isinstance(rec, (list, tuple)):
+        raise ValueError(f"{what}: record {k} is a polygon segmentation; only run-length records {{'size', 'counts'}} are decoded")
+    if not isinstance(rec, dict) or "size" not in rec or "counts" not in rec:
+        raise ValueError(f"{what}: record {k} is not a run-length record {{'size': [H, W], 'counts': str | bytes | list}}")
+    size = rec["size"]
+    if len(size) != 2:
+        raise ValueError(f"{what}: record {k}: size is [H, W]")
+    H, W = int(size[0]), int(size[1])
+    if H <= 0 or W <= 0 or H * W >= 1 << 31:
+        raise ValueError(f"{what}: record {k}: size {[H, W]} must be positive with H*W < 2^31")
+    c = rec["counts"]
+    if isinstance(c, str):
+        c = c.encode("ascii")
+    elif not isinstance(c, (bytes, bytearray)):
+        c = counts_to_string(c).encode("ascii")
+    return H, W, bytes(c)
+
+
+def as_record(rec):
+    """the string form of a run-length segmentation, as `decode` / `largest_component` read every record they are given:
+    {'size': [H, W], 'counts': str}; bytes are decoded, an uncompressed count list is converted with counts_to_string; a polygon
+    raises ValueError.  decode_numpy(as_record(r)) is the host's answer for any record the device calls accept."""
+    H, W, c = _as_record(rec, 0, "as_record")
+    return {"size": [H, W], "counts": c.decode("ascii")}
+
+
+def _prepare(records, groups, mode, what):
+    """host-side checks and tables, before any launch: (recs, sizes [G] of (H, W), group_start [G+1])"""
+    recs = [_as_record(r, k, what) for k, r in enumerate(records)]
+    K = len(recs)
+    if groups is None:
+        groups = [(1, (h, w)) for h, w, _ in recs]
+    starts, sizes = [0], []
+    for g, (n, size) in enumerate(groups):
+        n, H, W = int(n), int(size[0]), int(size[1])
+        if n < 0 or H <= 0 or W <= 0 or H * W >= 1 << 31:
+            raise ValueError(f"{what}: group {g}: a record count >= 0 and a positive size with H*W < 2^31 expected")
+        if mode == 1 and n != 1:
+            raise ValueError(f"{what}: group {g} holds {n} records; the largest component is taken of exactly one")
+        if starts[-1] + n > K:
+            raise ValueError(f"{what}: the groups take more than the {K} records given")
+        for k in range(starts[-1], starts[-1] + n):
+            if (recs[k][0], recs[k][1]) != (H, W):
+                raise ValueError(f"{what}: record {k} has size {[recs[k][0], recs[k][1]]}, its group {g} has {[H, W]}")
+        starts.append(starts[-1] + n)
+        sizes.append((H, W))
+    if starts[-1] != K:
+        raise ValueError(f"{what}: the groups take {starts[-1]} of the {K} records given")
+    return recs, sizes, starts
+
+
+def _decode_call(records, groups, mode, device, what):
+    import torch
+    recs, sizes, starts = _prepare(records, groups, mode, what)
+    K, G = len(recs), len(sizes)
+    if G == 0:
+        return [], None
+    from . import _lib as L
+    from .ops import _stream
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"unmore_amd.rle.{what} runs on the MI355X only (no CPU fallback); decode_numpy restates the format on the host")
+    # ---- every table and the characters in one buffer, one host-to-device copy
+    nchars = np.array([len(c) for _, _, c in recs], dtype=np.int64)
+    char_offsets = np.concatenate([[0], np.cumsum(nchars)]).astype(np.int64)
+    total_chars = int(char_offsets[-1])
+    out_desc = np.zeros((G, 3), dtype=np.int64)
+    off = 0
+    for g, (h, w) in enumerate(sizes):
+        out_desc[g] = (h, w, off)
+        off += (h * w + 15) & ~15                                            # every mask starts on a 16-byte boundary
+    out_bytes = off
+    seg_offsets = np.zeros(G + 1, dtype=np.int64)
+    if mode == 1:
+        seg_offsets[1:] = np.cumsum(nchars // 2 + 1 + np.array([w for _, w in sizes], dtype=np.int64))
+    total_segments = int(seg_offsets[-1])
+    gs = np.zeros((G + 2) & ~1, dtype=np.int32)
+    gs[:G + 1] = starts
+    tables = np.concatenate([char_offsets, out_desc.reshape(-1), seg_offsets, gs.view(np.int64)])
+    o_desc, o_seg, o_gs, o_chars = (K + 1) * 8, (K + 1 + 3 * G) * 8, (K + 1 + 3 * G + G + 1) * 8, tables.size * 8
+    host = np.concatenate([tables.view(np.uint8), np.frombuffer(b"".join(c for _, _, c in recs), dtype=np.uint8)])
+    with torch.cuda.device(device):
+        buf = torch.from_numpy(host).to(device)
+        out = torch.empty(out_bytes, dtype=torch.uint8, device=device)
+        status = torch.empty(max(K, 1), dtype=torch.int32, device=device)
+        info = torch.empty((G, 2), dtype=torch.int32, device=device) if mode == 1 else None
+        nbytes = L.lib().umr_rle_decode_workspace(K, total_chars, total_segments, mode)
+        ws = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device)
+        base = buf.data_ptr()
+        vp = ctypes.c_void_p
+        L.check(L.lib().umr_rle_decode(vp(base + o_chars), vp(base), K, total_chars, vp(base + o_desc), vp(base + o_gs), vp(base + o_seg), G,
+                                       max(h * w for h, w in sizes), total_segments, vp(out.data_ptr()), out_bytes, 255, mode,
+                                       vp(status.data_ptr()), vp(info.data_ptr()) if info is not None else None, vp(ws.data_ptr()), nbytes,
+                                       _stream()), "umr_rle_decode")
+        st = status[:K].cpu().numpy() if K else np.zeros(0, np.int32)         # the call's only synchronisation
+    masks = [out[int(o):int(o) + h * w].view(h, w) for (h, w), o in zip(sizes, out_desc[:, 2])]
+    bad = np.flatnonzero(st)
+    if bad.size:
+        k = int(bad[0])
+        why = "; ".join(t for b, t in _STATUS_BITS if int(st[k]) & b)
+        more = f" (also malformed: records {', '.join(str(int(b)) for b in bad[1:])})" if bad.size > 1 else ""
+        err = ValueError(f"{what}: record {k} is not a run-length string of a {recs[k][0]}x{recs[k][1]} mask: {why}{more}")
+        err.status, err.masks, err.info = st, masks, info     # what the well-formed records gave; a malformed one contributed nothing
+        raise err
+    return masks, info
+
+
+def decode(records, groups=None, device="cuda"):
+    """run-length records -> list of [h, w] u8 device tensors holding 0 / 255 (views into one packed buffer).  records: a list of
+    {'size': [H, W], 'counts': str | bytes} or of uncompressed records whose counts are a list (converted with counts_to_string);
+    polygon segmentations raise ValueError.  groups=None: one mask per record.  Otherwise a list of (n, (H, W)): output g is the
+    union (OR) of the next n records, all of size (H, W); n = 0 gives an all-zero mask.  The strings are parsed on the device
+    (csrc/rle_decode.hip); one host-to-device copy carries the tables and the characters; the status words are read back once after
+    the launches -- the call's only synchronisation -- and a malformed string raises ValueError naming its record.  That error
+    carries what the call did make: `.status` (int32 numpy array, one word per record, the bits of umr_rle_decode), `.masks` (the list
+    the call would have returned; a malformed record contributed nothing to its mask) and `.info` (None here).  Argument errors
+    (non-positive sizes, mixed sizes inside a group) are raised before any launch and carry none of these."""
+    return _decode_call(records, groups, 0, device, "decode")[0]
+
+
+def largest_component(records, device="cuda"):
+    """per record the largest 4-connected component of its mask, as utils/preprocess_votecut.py:88-92 takes it
+    (cv2.connectedComponentsWithStats(mask, 4), np.argmax of the areas: ties go to the component whose first pixel in raster order
+    comes first).  Returns (masks, info): masks as `decode` returns them; info int32 [K, 2] on the device = (number of components,
+    area of the kept one), (0, 0) for an empty mask.  Runs are labelled, not pixels: see csrc/rle_decode.hip.  A malformed string
+    raises ValueError as in `decode`, with `.status`, `.masks` (all zero for the malformed record) and `.info` attached."""
+    masks, info = _decode_call(records, None, 1, device, "largest_component")
+    if info is None:
+        import torch
+        info = torch.empty((0, 2), dtype=torch.int32, device=device)
+    return masks, info
