@@ -409,6 +409,45 @@ int umr_rle_decode(const uint8_t* chars, const int64_t* char_offsets, int K, int
                    const int32_t* group_start, const int64_t* seg_offsets, int G, int64_t max_pixels, int64_t total_segments, uint8_t* out,
                    int64_t out_bytes, int value, int mode, int32_t* status, int32_t* info, void* workspace, int64_t workspace_bytes,
                    umr_stream_t stream);
+/* COCO AP / AR evaluation (pycocotools' cocoeval.py as COCO_evaluator/coco_evaluation.py reaches it through COCOeval_opt): the two hot
+ * loops, pairwise IoU and the greedy per-threshold matching.  An evaluation unit is one (image, category) pair; unit u owns the records
+ * unit_start[u] .. unit_start[u+1]-1 (int32 [U+1], ascending, unit_start[0] == 0, unit_start[U] == K): first its unit_nd[u] detections,
+ * in descending score order, then its ground truths.  The D_u x G_u matrices are packed row-major at pair_offsets[u] (int64 [U+1], the
+ * caller's prefix sum of D_u * G_u; total_pairs = pair_offsets[U]).  crowd: uint8 [K], read for ground-truth records only.
+ * mask_iou: the records are run-length strings packed as rle_decode takes them (chars, char_offsets); unit_size: int64 [U][3] =
+ *   (H, W, 0), all masks of a unit share it.  inter = the integer intersection counts, area[k] = the integer area of record k, iou =
+ *   (double)i / (double)(a_d + a_g - i), (double)i / (double)a_d for a crowd ground truth, 0 when that denominator is 0.  Masks are
+ *   painted as bit sets over the format's column-major pixel order, 64 pixels per word, never as bytes: word_offsets (int64 [K+1]) is
+ *   the caller's prefix sum of (H*W + 63) / 64 per record, total_words = word_offsets[K].  status[k] as rle_decode gives it; a record
+ *   with non-zero status has area 0 and intersects nothing, the others are unaffected.  max_pixels / max_d / max_g: the largest H*W,
+ *   D_u and G_u.  Workspace: mask_iou_workspace(K, total_chars, total_words) bytes, 8-byte aligned.  Three launches after the parse.
+ * box_iou: boxes double [K][4] as x, y, w, h; pycocotools' bbIou in its operation order, without fused multiply-add:
+ *   w = min(dx+dw, gx+gw) - max(dx, gx), 0 if w <= 0; h likewise; i = w*h; u = dw*dh + gw*gh - i (dw*dh for a crowd); i/u.
+ *   max_pairs: the largest D_u * G_u.
+ * coco_match: evaluateImg for every (unit, area range, threshold).  unit_nd / unit_ng: int32 [U]; det_offsets / gt_offsets: int64 [U+1]
+ *   prefix sums of D_u / G_u into dt_area / gt_area (double) and gt_crowd (uint8); area_rng: double [A][2], both bounds inclusive; thr:
+ *   double [T], used as passed.  A ground truth is ignored in range a when it is a crowd or its area is outside the range; per detection
+ *   (the first max_det of a unit, in order) the bar starts at min(t, 1 - 1e-10); ground truths are visited non-ignored first, each
+ *   group in order; one already matched and not a crowd is skipped; once a non-ignored one is held the walk stops at the first
+ *   ignored one; a candidate replaces the held one when its IoU >= the bar (equal IoU: the later one); the detection inherits its
+ *   match's ignore flag; an unmatched detection whose own area is outside the range is ignored.  Outputs, unit u at det_offsets[u]*A*T +
+ *   ((a*T + t)*D_u + d): dt_matched (uint8), dt_gt (int32, the ground truth's index inside its unit or -1), dt_ignore (uint8);
+ *   detections beyond max_det get (0, -1, 1).  gt_ignore (uint8) at gt_offsets[u]*A + a*G_u + g; gt_matched (uint8) at
+ *   gt_offsets[u]*A*T + (a*T + t)*G_u + g.  A unit whose table entries point outside the buffers is left unwritten.
+ * The caller owns every buffer; no synchronisation; the same input gives the same bytes on every run. */
+int64_t umr_mask_iou_workspace(int K, int64_t total_chars, int64_t total_words);
+int umr_mask_iou(const uint8_t* chars, const int64_t* char_offsets, int K, int64_t total_chars, const int64_t* unit_size,
+                 const int32_t* unit_start, const int32_t* unit_nd, const int64_t* pair_offsets, const int64_t* word_offsets,
+                 const uint8_t* crowd, int U, int64_t max_pixels, int max_d, int max_g, int64_t total_pairs, int64_t total_words,
+                 int32_t* inter, double* iou, int32_t* area, int32_t* status, void* workspace, int64_t workspace_bytes,
+                 umr_stream_t stream);
+int umr_box_iou(const double* boxes, const int32_t* unit_start, const int32_t* unit_nd, const int64_t* pair_offsets, const uint8_t* crowd,
+                int U, int K, int64_t max_pairs, int64_t total_pairs, double* iou, umr_stream_t stream);
+int umr_coco_match(const double* iou, const int64_t* pair_offsets, int64_t total_pairs, const int32_t* unit_nd, const int32_t* unit_ng,
+                   const int64_t* det_offsets, int64_t total_dets, const int64_t* gt_offsets, int64_t total_gts, const double* dt_area,
+                   const double* gt_area, const uint8_t* gt_crowd, const double* area_rng, int A, const double* thr, int T, int max_det,
+                   int U, uint8_t* dt_matched, int32_t* dt_gt, uint8_t* dt_ignore, uint8_t* gt_ignore, uint8_t* gt_matched,
+                   umr_stream_t stream);
 /* mask_components: 8-connected components of every map's union mask (sigmoid(sdf) > 0.5 | ||center|| > 0.5) in scipy.ndimage.label's
  * order (by first pixel in raster order) -- object_reasoning.py:206-257, the --analyze_cc branch of center_reasoning (README.md:176).
  * counts[b] = the number of components of map b; boxes[b][i] = [x1, y1, x2, y2) of component i for i < min(counts[b], max_components),

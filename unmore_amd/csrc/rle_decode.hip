@@ -365,6 +365,16 @@ bool rd_sizes_ok(int K, int64_t total_chars, int64_t total_segments) {
 
 }  // namespace
 
+int umr_rle_parse_launch(const uint8_t* chars, const int64_t* char_offsets, int K, int64_t total_chars, const int64_t* out_desc,
+                         const int32_t* group_start, int G, int64_t out_bytes, int32_t* status, int32_t* nruns, long long* num,
+                         uint32_t* starts, hipStream_t stream) {
+    if (K <= 0) return UMR_OK;
+    hipLaunchKernelGGL(rle_parse_kernel, dim3(K), dim3(RD_THREADS), 0, stream, chars, char_offsets, total_chars, out_desc, group_start, G,
+                       out_bytes, status, nruns, num, starts);
+    UMR_LAUNCH_CHECK();
+    return UMR_OK;
+}
+
 extern "C" int64_t umr_rle_decode_workspace(int K, int64_t total_chars, int64_t total_segments, int mode) {
     if (!rd_sizes_ok(K, total_chars, total_segments) || (mode != 0 && mode != 1)) return -1;
     const int64_t slots = total_chars + K;

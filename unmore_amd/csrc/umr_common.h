@@ -131,3 +131,10 @@ int umr_f32_mode_now();   // umr_api.hip: UMR_F32_EXACT / UMR_F32_X3
 int umr_cu_budget_now();  // umr_api.hip: 0 = every CU, n = the persistent GEMM grids occupy at most n CUs
 #define UMR_CHECK_ARG(cond, msg) do { if (!(cond)) return umr_set_error(UMR_ERR_INVALID, msg); } while (0)
 #define UMR_LAUNCH_CHECK() do { hipError_t e_ = hipGetLastError(); if (e_ != hipSuccess) return umr_set_error(UMR_ERR_HIP - (int)e_, hipGetErrorString(e_)); } while (0)
+
+// rle_decode.hip: the strings -> runs pass of umr_rle_decode alone (one launch, no synchronisation), for callers that consume the runs
+// themselves (coco_eval.hip).  Record k's runs: starts[char_offsets[k] + k ...), nruns[k] of them, run i set iff i is odd; status[k] as
+// umr_rle_decode documents it.  num and starts hold total_chars + K slots each; sizes as out_desc's (H, W, byte offset < out_bytes).
+int umr_rle_parse_launch(const uint8_t* chars, const int64_t* char_offsets, int K, int64_t total_chars, const int64_t* out_desc,
+                         const int32_t* group_start, int G, int64_t out_bytes, int32_t* status, int32_t* nruns, long long* num,
+                         uint32_t* starts, hipStream_t stream);
