@@ -409,6 +409,24 @@ int umr_rle_decode(const uint8_t* chars, const int64_t* char_offsets, int K, int
                    const int32_t* group_start, const int64_t* seg_offsets, int G, int64_t max_pixels, int64_t total_segments, uint8_t* out,
                    int64_t out_bytes, int value, int mode, int32_t* status, int32_t* info, void* workspace, int64_t workspace_bytes,
                    umr_stream_t stream);
+/* poly_rle: the run-length records of POLYGON segmentations (pycocotools' annToRLE: maskApi.c rleFrPoly per polygon, rleMerge = union
+ * over an annotation's polygons).  xy: double [n_vertices][2], the polygons' vertices one after the other; polygon q = vertices
+ * poly_offsets[q] .. poly_offsets[q+1]-1 (int64 [n_polygons+1], at least one vertex each); annotation a = polygons ann_polys[a] ..
+ * ann_polys[a+1]-1 (int64 [n_annotations+1]; none: an empty mask) on an image of ann_sizes[a] = (H, W) (int64 [n_annotations][2], H*W <
+ * 2^31).  cross_offsets (int64 [n_polygons+1], crossing_capacity = cross_offsets[n_polygons]): the caller's prefix sum of an upper
+ * bound of every polygon's column crossings -- sum over its edges of min(dx, W) + 1, dx = |x[j+1] - x[j]| with x = (int)(5*xy + .5);
+ * a polygon's crossings beyond its bound are dropped, never stored elsewhere.  |xy| <= 2^20 and finite (the caller checks).
+ * All double arithmetic is uncontracted IEEE in maskApi.c's operation order.  phases: a mask of 1 = the crossings, 2 = their sort,
+ * 4 = the characters; 4 is the measure pass (chars == NULL) or the write pass of umr_rle_encode, over the workspace that phases 1 and
+ * 2 of an earlier call on the same tables left: a caller runs 7 to measure, then 4 to write.  Every store is guarded by the record's
+ * own slice and by crossing_capacity / chars_capacity.  The caller owns every buffer; workspace >= poly_rle_workspace(n_vertices,
+ * n_polygons, n_annotations, crossing_capacity) bytes, 8-byte aligned.  One launch per phase, no atomics, no synchronisation; the same
+ * input gives the same bytes on every run. */
+int64_t umr_poly_rle_workspace(int64_t n_vertices, int n_polygons, int n_annotations, int64_t crossing_capacity);
+int umr_poly_rle(const double* xy, const int64_t* poly_offsets, const int64_t* ann_polys, const int64_t* ann_sizes,
+                 const int64_t* cross_offsets, int64_t n_vertices, int n_polygons, int n_annotations, int64_t crossing_capacity, int phases,
+                 int64_t* sizes, const int64_t* offsets, uint8_t* chars, int64_t chars_capacity, void* workspace, int64_t workspace_bytes,
+                 umr_stream_t stream);
 /* COCO AP / AR evaluation (pycocotools' cocoeval.py as COCO_evaluator/coco_evaluation.py reaches it through COCOeval_opt): the two hot
  * loops, pairwise IoU and the greedy per-threshold matching.  An evaluation unit is one (image, category) pair; unit u owns the records
  * unit_start[u] .. unit_start[u+1]-1 (int32 [U+1], ascending, unit_start[0] == 0, unit_start[U] == K): first its unit_nd[u] detections,

@@ -143,6 +143,8 @@ _SIGS = {
     "umr_mask_paste_rle": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp],
     "umr_rle_decode_workspace": [_i32, _i64, _i64, _i32],
     "umr_rle_decode": [_vp, _vp, _i32, _i64, _vp, _vp, _vp, _i32, _i64, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp],
+    "umr_poly_rle_workspace": [_i64, _i32, _i32, _i64],
+    "umr_poly_rle": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp],
     "umr_mask_iou_workspace": [_i32, _i64, _i64],
     "umr_mask_iou": [_vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
     "umr_box_iou": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _vp, _vp],
@@ -198,7 +200,8 @@ def lib():
         for fn in ("umr_gemm_tn_workspace", "umr_layernorm_bwd_workspace", "umr_head_out_bwd_workspace", "umr_loss_workspace",
                    "umr_linear_head_bwd_weight_workspace", "umr_linear_head_shift9_workspace", "umr_label_synthesis_workspace", "umr_attention_bwd_workspace",
                    "umr_distance_transform_workspace", "umr_gemm_nt_workspace", "umr_gemm_nt_x3_workspace", "umr_nms_workspace",
-                   "umr_bn_train_workspace", "umr_bg_square_workspace", "umr_rle_decode_workspace", "umr_mask_iou_workspace"):
+                   "umr_bn_train_workspace", "umr_bg_square_workspace", "umr_rle_decode_workspace", "umr_mask_iou_workspace",
+                   "umr_poly_rle_workspace"):
             getattr(_lib, fn).restype = ctypes.c_int64
     return _lib
 

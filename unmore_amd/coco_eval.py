@@ -10,8 +10,10 @@ stable sort by score, cumulative sums, the precision envelope and the 101 recall
 Data rules are pycocotools' (`loadRes`, `_prepare`): images = the ground truth's image ids, ascending (or `img_ids`); categories = the
 ground truth's category ids, ascending; ignore = iscrowd; a ground truth's area is the file's `area`; a detection's area is its mask's
 area for `segm` (its `bbox` is dropped, coco_evaluation.py:601-608) and w*h for `bbox`; a detection on an unknown image raises
-ValueError.  Polygon ground truths are out of scope for `segm` (they need pycocotools' own rasteriser to give pycocotools' numbers): a
-polygon raises ValueError naming its annotation; `bbox` reads only bbox / area / iscrowd and takes any ground truth."""
+ValueError.  Polygon ground truths (COCO's own annotation files) are rasterised on the device by pycocotools' rule (rle.from_polygons,
+csrc/poly_rle.hip) when asked for: `COCOEvaluator(gt, polygons="rasterize")` converts them once at construction, `convert_polygons`
+converts a file once; by default a polygon raises ValueError naming its annotation.  `bbox` reads only bbox / area / iscrowd and takes
+any ground truth."""
 import copy
 import json
 import os
@@ -306,18 +308,55 @@ def summarize(ev, max_dets, iou_thrs=IOU_THRS):
                      one(0, area="small", max_det=md[2]), one(0, area="medium", max_det=md[2]), one(0, area="large", max_det=md[2])], dtype=np.float64)
 
 
+# ---------------------------------------------------------------------------------------------------------------- polygon ground truths
+def _is_polygon(seg):
+    return isinstance(seg, (list, tuple))
+
+
+def convert_polygons(gt_or_path, out_path=None, device="cuda"):
+    """the one-time conversion of a ground-truth file whose annotations carry polygon segmentations (COCO's instances_*.json and the
+    class-agnostic files made from it): every polygon `segmentation` becomes the run-length record pycocotools' annToRLE gives, in one
+    `rle.from_polygons` call with the sizes of the ground truth's `images`.  Run-length segmentations, `area`, `bbox` and everything else
+    stay as the file has them.  Returns the converted ground truth (the input is not modified) and writes it to out_path when given."""
+    gt = gt_or_path
+    if not isinstance(gt, dict):
+        with open(gt) as f:
+            gt = json.load(f)
+    size_of = {im["id"]: (int(im["height"]), int(im["width"])) for im in gt["images"]}
+    which = [i for i, g in enumerate(gt["annotations"]) if _is_polygon(g.get("segmentation"))]
+    for i in which:
+        g = gt["annotations"][i]
+        if g["image_id"] not in size_of:
+            raise ValueError(f"convert_polygons: annotation {g.get('id')!r} is on image {g['image_id']!r}, which the ground truth does not have")
+    out = dict(gt)
+    if which:
+        anns = gt["annotations"]
+        recs = rle.from_polygons([anns[i]["segmentation"] for i in which], [size_of[anns[i]["image_id"]] for i in which], device=device)
+        out["annotations"] = list(anns)
+        for i, rec in zip(which, recs):
+            out["annotations"][i] = dict(anns[i], segmentation=rec)
+    if out_path is not None:
+        with open(out_path, "w") as f:
+            json.dump(out, f)
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------- the evaluator
 class COCOEvaluator:
     """The surface COCO_evaluator/coco_evaluation.py:37-220 gives main.py: reset(), process(image_id, coco_instances), evaluate(img_ids).
     gt: the path of a COCO ground-truth file or the loaded dict.  evaluate() returns {"bbox": {...}, "segm": {...}} with the twelve names
     of METRICS, values x100 and nan where the statistic is -1; afterwards `.eval[task]` holds precision [T,R,K,A,M], recall [T,K,A,M] and
-    scores [T,R,K,A,M] (float64, -1 where undefined) and `.stats[task]` the twelve raw statistics."""
+    scores [T,R,K,A,M] (float64, -1 where undefined) and `.stats[task]` the twelve raw statistics.  polygons: "raise" (a polygon
+    ground truth makes the segm task raise ValueError) or "rasterize" (every polygon ground truth is converted here, once, by
+    `convert_polygons`; the segm task then sees run-length records only)."""
 
-    def __init__(self, gt, tasks=("bbox", "segm"), max_dets_per_image=None, device="cuda"):
+    def __init__(self, gt, tasks=("bbox", "segm"), max_dets_per_image=None, device="cuda", polygons="raise"):
+        if polygons not in ("raise", "rasterize"):
+            raise ValueError(f"COCOEvaluator: polygons={polygons!r}; 'raise' or 'rasterize' expected")
         if not isinstance(gt, dict):
             with open(gt) as f:
                 gt = json.load(f)
-        self.gt = gt
+        self.gt = convert_polygons(gt, device=device) if polygons == "rasterize" else gt
         self.tasks = tuple(tasks)
         for t in self.tasks:
             if t not in ("bbox", "segm"):
@@ -358,9 +397,9 @@ class COCOEvaluator:
         max_dets = sorted(self.max_dets)
         gts, dts = {}, {}
         for g in gt["annotations"]:
-            if task == "segm" and isinstance(g.get("segmentation"), (list, tuple)):
+            if task == "segm" and _is_polygon(g.get("segmentation")):
                 raise ValueError(f"COCOEvaluator: ground-truth annotation {g.get('id')!r} has a polygon segmentation; the segm task takes "
-                                 "run-length segmentations (convert the file once with pycocotools' annToRLE)")
+                                 "run-length segmentations (pass polygons='rasterize', or convert the file once with convert_polygons)")
             gts.setdefault((g["image_id"], g["category_id"]), []).append(g)
         for r in results:
             dts.setdefault((r["image_id"], r["category_id"]), []).append(r)

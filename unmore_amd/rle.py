@@ -7,8 +7,9 @@ c = x & 0x1f and x >>= 5 (arithmetic) another group follows iff (x != -1 if c & 
 has 0x20 set; every group is the character chr(c + 48).  A record is {"size": [H, W], "counts": str}.
 
 `encode` / `encode_pasted` run on the device (csrc/rle.hip): a measure pass, one small read of the sizes, a write pass into a packed
-buffer, one read of the characters -- nothing image-sized crosses to the host.  The *_numpy functions restate the format on the CPU:
-what the tests compare the kernels against and what a host without a GPU reads the file back with."""
+buffer, one read of the characters -- nothing image-sized crosses to the host.  `from_polygons` (csrc/poly_rle.hip) makes the records
+of polygon segmentations by pycocotools' annToRLE rule through the same two passes.  The *_numpy functions restate the format and the
+polygon rule on the CPU: what the tests compare the kernels against and what a host without a GPU reads the file back with."""
 import ctypes
 
 import numpy as np
@@ -99,6 +100,124 @@ def to_bbox(rle):
     return [float(x1), float(y1), float(x2 - x1 + 1), float(y2 - y1 + 1)]
 
 
+# ---------------------------------------------------------------------------------------------------------------- polygons on the CPU
+# pycocotools' annToRLE for a polygon segmentation: maskApi.c's rleFrPoly per polygon, then rleMerge (union) over the annotation's
+# polygons, restated sequentially, loop by loop, in plain Python floats (IEEE doubles; int() truncates toward zero as C's (int) does).
+# A polygon's vertices are scaled by 5, every edge is walked point by point on that fine grid, a "crossing" is recorded wherever the
+# walk steps over the centre line of a pixel column inside the image, at the pixel row the walk is at; pixel p = x*H + y (column-major)
+# is set iff an odd number of crossings lie at or before it.
+POLY_SCALE = 5.0
+POLY_MAX_COORD = float(1 << 20)
+
+
+def _poly_vertices(xy):
+    """step 1: flat [x0, y0, x1, y1, ...] -> integer vertices on the fine grid (lists x, y of k ints, not yet closed)"""
+    k = len(xy) // 2
+    x = [int(POLY_SCALE * float(xy[2 * j]) + .5) for j in range(k)]
+    y = [int(POLY_SCALE * float(xy[2 * j + 1]) + .5) for j in range(k)]
+    return x, y
+
+
+def polygon_points_numpy(xy):
+    """steps 1-2: the points (u, v) along the closed outline, all edges concatenated in order (two int lists)"""
+    x, y = _poly_vertices(xy)
+    k = len(x)
+    x.append(x[0])
+    y.append(y[0])
+    u, v = [], []
+    for j in range(k):
+        xs, xe, ys, ye = x[j], x[j + 1], y[j], y[j + 1]
+        dx, dy = abs(xe - xs), abs(ys - ye)
+        flip = (dx >= dy and xs > xe) or (dx < dy and ys > ye)
+        if flip:
+            xs, xe, ys, ye = xe, xs, ye, ys
+        if dx >= dy:
+            s = float(ye - ys) / dx if dx > 0 else 0.0        # a zero-length edge: one point, its v is never used
+            for d in range(dx + 1):
+                t = dx - d if flip else d
+                u.append(t + xs)
+                v.append(int(ys + s * t + .5))
+        else:
+            s = float(xe - xs) / dy
+            for d in range(dy + 1):
+                t = dy - d if flip else d
+                v.append(t + ys)
+                u.append(int(xs + s * t + .5))
+    return u, v
+
+
+def polygon_crossings_numpy(xy, h, w):
+    """steps 1-3: the crossings a = xd*h + yd of one polygon on an h x w image, in the order the outline meets them (int64 array;
+    a value can equal h*w)"""
+    u, v = polygon_points_numpy(xy)
+    out = []
+    for j in range(1, len(u)):
+        if u[j] == u[j - 1]:
+            continue
+        xd = float(u[j] if u[j] < u[j - 1] else u[j] - 1)
+        xd = (xd + .5) / POLY_SCALE - .5
+        if np.floor(xd) != xd or xd < 0 or xd > w - 1:
+            continue
+        yd = float(v[j] if v[j] < v[j - 1] else v[j - 1])
+        yd = (yd + .5) / POLY_SCALE - .5
+        if yd < 0:
+            yd = 0.0
+        elif yd > h:
+            yd = float(h)
+        yd = np.ceil(yd)
+        out.append(int(xd) * h + int(yd))
+    return np.asarray(out, dtype=np.int64)
+
+
+def polygon_mask_numpy(xy, h, w):
+    """step 4: [h, w] u8, pixel p = x*h + y set iff the number of crossings <= p is odd"""
+    a = polygon_crossings_numpy(xy, h, w)
+    hits = np.bincount(a[a < h * w], minlength=h * w)
+    return (np.cumsum(hits) & 1).astype(np.uint8).reshape((h, w), order="F")
+
+
+def _check_polygons(segmentations, sizes, what):
+    """the restrictions, before anything is computed: (list of lists of float64 arrays, list of (H, W))"""
+    n = len(segmentations)
+    if len(sizes) == 2 and not isinstance(sizes[0], (list, tuple, np.ndarray)):
+        sizes = [sizes] * n
+    if len(sizes) != n:
+        raise ValueError(f"{what}: {n} segmentations, {len(sizes)} sizes")
+    polys, out_sizes = [], []
+    for i, (seg, size) in enumerate(zip(segmentations, sizes)):
+        if isinstance(seg, dict) or not isinstance(seg, (list, tuple)) or any(not isinstance(p, (list, tuple, np.ndarray)) for p in seg):
+            raise ValueError(f"{what}: segmentation {i} is not a polygon segmentation (a list of flat coordinate lists)")
+        H, W = int(size[0]), int(size[1])
+        if H <= 0 or W <= 0 or H * W >= 1 << 31:
+            raise ValueError(f"{what}: segmentation {i}: size {[H, W]} must be positive with H*W < 2^31")
+        mine = []
+        for q, p in enumerate(seg):
+            c = np.asarray(p, dtype=np.float64).reshape(-1)
+            if c.size == 0 or c.size % 2:
+                raise ValueError(f"{what}: segmentation {i}, polygon {q}: {c.size} coordinates; a non-empty list of x, y pairs is expected")
+            if not np.isfinite(c).all():
+                raise ValueError(f"{what}: segmentation {i}, polygon {q}: a coordinate is not finite")
+            if (np.abs(c) > POLY_MAX_COORD).any():
+                raise ValueError(f"{what}: segmentation {i}, polygon {q}: a coordinate is beyond 2^20 in magnitude")
+            mine.append(c)
+        polys.append(mine)
+        out_sizes.append((H, W))
+    return polys, out_sizes
+
+
+def from_polygons_numpy(segmentations, sizes):
+    """step 5: the records of polygon segmentations on the CPU.  segmentations[i]: a list of flat [x0, y0, x1, y1, ...] lists; sizes:
+    one (H, W) or one per segmentation.  The mask is the OR of the polygons' masks, the record its canonical string."""
+    polys, sizes = _check_polygons(segmentations, sizes, "from_polygons_numpy")
+    out = []
+    for mine, (H, W) in zip(polys, sizes):
+        m = np.zeros((H, W), np.uint8)
+        for c in mine:
+            m |= polygon_mask_numpy(c, H, W)
+        out.append(encode_numpy(m))
+    return out
+
+
 # ---------------------------------------------------------------------------------------------------------------- on the device
 def _two_pass(launch, K, H, W, device):
     """measure -> sizes to the host -> packed write -> characters to the host; `launch(sizes, offsets, chars, capacity)` enqueues a pass"""
@@ -152,6 +271,92 @@ def encode_pasted(sdf, center, int_boxes, select, H, W):
         L.check(L.lib().umr_mask_paste_rle(_p(sdf), _p(center), _p(int_boxes), _p(select), K, S, H, W, _p(sizes), _p(offsets), _p(chars), cap,
                                            _stream()), "umr_mask_paste_rle")
     return _two_pass(launch, K, H, W, sdf.device)
+
+
+POLY_SORT_LDS_KEYS = 4096      # csrc/poly_rle.hip POLY_LDS_KEYS: crossing lists up to this length are sorted in LDS, longer ones in memory
+
+
+def _poly_tables(polys, sizes):
+    """the packed upload of `from_polygons`: float64 coordinates, then int64 polygon offsets (in vertices), annotation polygon ranges,
+    annotation sizes and the crossing slices (prefix sums of the bound sum over edges of min(dx, W) + 1 -- an edge's u is monotone, so
+    it steps over every column line at most once, and once more where it joins the previous edge).  Returns (host u8 array, byte
+    offsets of the five tables, V, NP, NA, C)."""
+    flat = [c for mine in polys for c in mine]
+    NA, NP = len(polys), len(flat)
+    nv = np.array([c.size // 2 for c in flat], dtype=np.int64)
+    poly_off = np.concatenate([[0], np.cumsum(nv)]).astype(np.int64)
+    ann_poly = np.concatenate([[0], np.cumsum([len(mine) for mine in polys])]).astype(np.int64)
+    ann_size = np.array(sizes, dtype=np.int64).reshape(NA, 2)
+    xy = np.concatenate(flat + [np.zeros(2)]).astype(np.float64)             # never empty
+    V = int(poly_off[-1])
+    bound = np.zeros(NP, dtype=np.int64)
+    if NP:
+        x = np.trunc(POLY_SCALE * xy[0:2 * V:2] + .5).astype(np.int64)       # step 1's formula
+        nxt = np.arange(V) + 1
+        nxt[poly_off[1:] - 1] = poly_off[:-1]                                # the ring closes on the polygon's first vertex
+        w_of_poly = np.repeat(ann_size[:, 1], np.diff(ann_poly))
+        per_edge = np.minimum(np.abs(x[nxt] - x), np.repeat(w_of_poly, nv)) + 1
+        bound = np.add.reduceat(per_edge, poly_off[:-1])
+    cross_off = np.concatenate([[0], np.cumsum(bound)]).astype(np.int64)
+    tables = [xy.view(np.uint8), poly_off.view(np.uint8), ann_poly.view(np.uint8), ann_size.reshape(-1).view(np.uint8), cross_off.view(np.uint8)]
+    offs = np.concatenate([[0], np.cumsum([t.size for t in tables])])[:-1]
+    return np.concatenate(tables), [int(o) for o in offs], V, NP, NA, int(cross_off[-1])
+
+
+def from_polygons(segmentations, sizes, device="cuda", phase_ms=None):
+    """pycocotools' annToRLE for polygon segmentations, on the device (csrc/poly_rle.hip).  segmentations[i]: a COCO polygon
+    `segmentation`, i.e. a list of flat [x0, y0, x1, y1, ...] lists (the annotation's mask is the union of its polygons); sizes: one
+    (H, W) or one per segmentation.  Returns the records {'size': [H, W], 'counts': str}, byte for byte what `from_polygons_numpy`
+    gives.  One host-to-device copy carries the coordinates and the tables, two small reads come back (the sizes, then the packed
+    strings).  A coordinate list of odd length, a non-finite coordinate, one beyond 2^20 in magnitude and H*W >= 2^31 raise
+    ValueError before any launch.  phase_ms: a dict that receives the device time of the three phases (tools/polygon_rle_bench.py)."""
+    import torch
+    polys, sizes = _check_polygons(segmentations, sizes, "from_polygons")
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("unmore_amd.rle.from_polygons runs on the MI355X only (no CPU fallback); from_polygons_numpy restates it on the host")
+    if not polys:
+        return []
+    from . import _lib as L
+    from .ops import _p, _stream
+    host, (o_xy, o_po, o_ap, o_as, o_co), V, NP, NA, C = _poly_tables(polys, sizes)
+    if C >= 1 << 31 or V >= 1 << 31:
+        raise ValueError("from_polygons: more than 2^31 vertices or possible crossings in one call; split the batch")
+    vp = ctypes.c_void_p
+    with torch.cuda.device(device):
+        buf = torch.from_numpy(host).to(device)
+        nbytes = L.lib().umr_poly_rle_workspace(V, NP, NA, C)
+        ws = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device)
+        base = buf.data_ptr()
+
+        def run(phases, sizes_t, offsets, chars, cap):
+            L.check(L.lib().umr_poly_rle(vp(base + o_xy), vp(base + o_po), vp(base + o_ap), vp(base + o_as), vp(base + o_co), V, NP, NA, C, phases,
+                                         _p(sizes_t), _p(offsets), _p(chars), cap, vp(ws.data_ptr()), nbytes, _stream()), "umr_poly_rle")
+
+        def launch(sizes_t, offsets, chars, cap):
+            if chars is not None:                                          # the write pass reads what the measure pass left in the workspace
+                if phase_ms is None:
+                    return run(4, sizes_t, offsets, chars, cap)
+                t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                t0.record()
+                run(4, sizes_t, offsets, chars, cap)
+                t1.record()
+                t1.synchronize()
+                phase_ms["characters"] += t0.elapsed_time(t1)             # measure pass + write pass
+                return None
+            if phase_ms is None:
+                return run(7, sizes_t, offsets, chars, cap)
+            marks = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
+            for i, phases in enumerate((1, 2, 4)):
+                marks[i].record()
+                run(phases, sizes_t, offsets, chars, cap)
+            marks[3].record()
+            marks[3].synchronize()
+            phase_ms.update({k: marks[i].elapsed_time(marks[i + 1]) for i, k in enumerate(("generate", "sort", "characters"))})
+        out = _two_pass(launch, NA, 0, 0, device)
+    for rec, (H, W) in zip(out, sizes):
+        rec["size"] = [H, W]
+    return out
 
 
 # ---------------------------------------------------------------------------------------------------------------- strings -> masks
