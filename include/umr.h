@@ -621,6 +621,52 @@ int umr_bg_square(const umr_ragged_src* items, int32_t* out, void* workspace, in
 int umr_crop_resize_ragged(const umr_ragged_src* items, const int32_t* boxes, float* dst, float* mask_out, float* mask_sum,
                            int B, int C, int Ho, int Wo, umr_stream_t stream);
 
+/* ---- copy-paste augmentation of the detector's training batches (cad/engine/train_loop.py:90-248, called from run_step :261-263;
+ * csrc/copy_paste.hip) -----------------------------------------------------------------------------------------------------
+ * A RAGGED batch of P independent pairs, one device table entry each, one sequence of launches for all of them.  Per pair: the nc
+ * chosen masks choice[choice_off .. choice_off + nc) (indices into the labeled item's Nl masks) and the labeled image are resized to
+ * h_new x w_new (F.interpolate, bilinear, align_corners=False: src = fmaf(r, dst + 0.5, -0.5) clamped at 0 with r = rh / rw, the float32
+ * quotients in / out formed by the caller; a mask pixel is set iff a tap with a non-zero weight is set, an image byte is the float32
+ * value truncated) and pasted at (h_shift, w_shift) into the unlabeled frame.  Copied instance i is kept iff for every existing
+ * mask j: area_j > 0 and 2 * inter_ij < area_j (the reference's float32 inter / area < 0.5, max over j, NaN from an empty existing mask
+ * included; exact for Hu * Wu < 2^24, larger frames are refused); with Nu == 0 every copy is kept.  alpha = the union of the kept
+ * pasted masks; out_image [3,Hu,Wu] = alpha ? resized labeled : unlabeled; out_masks [Nu + nc,Hu,Wu] u8 (0 / 1) = the existing masks
+ * & ~alpha, then the kept pasted masks (rows of copies that are not kept are left unwritten).  A pair that keeps no copy writes
+ * neither: its result is the unlabeled item.  Masks are read as u8, non-zero = set.
+ * stats: int32 [total_rows][2], boxes: float [total_rows][4]; the pair's rows are row_off .. row_off + Nu + nc - 1, existing first.
+ *   stats[r] = (flag, area): a copied row's flag = kept; an existing row's flag = the pair keeps at least one copy.  area and box are
+ *   written for rows with a non-zero flag: the area of the output mask, and its box by Detectron2's BitMasks.get_bounding_boxes rule
+ *   [x_min, y_min, x_max + 1, y_max + 1] (zeros for an empty mask) when Nu > 0; with Nu == 0 the reference's own float32 box: the chosen
+ *   box of l_boxes ([Nl,4] XYXY) times (sx, sy), then x0, x1 += h_shift and y0, y1 += w_shift -- the reference swaps the two shifts
+ *   (:191-194) and so does this.  The caller zeroes stats before the call.
+ * word_off / inter_off: the pair's slices of the workspace's two regions, (nc + Nu + 1) * Hu * ceil(Wu / 64) 64-bit words (the bit
+ *   sets of the pasted masks, the existing masks and alpha) and (nc + 1) * Nu int32 (intersections, existing areas); total_words /
+ *   total_inter = the regions' sizes, workspace >= copy_paste_workspace(total_words, total_inter) bytes, 8-byte aligned.
+ *   max_words_per_mask, max_nc, max_nu: the largest Hu * ceil(Wu / 64), nc and Nu in the table (grid sizes only).
+ * phases: a mask of 1 = pack (resize, paste, bit sets), 2 = overlap + keep decision, 4 = compose + areas and boxes; a caller that
+ *   times the parts runs 1, 2, 4 one after the other on the same buffers, everyone else passes 7.
+ * An entry that breaks its own bounds (sizes, shifts, slices past the totals, nc > Nl) is skipped on the device: nothing of it is read
+ * or written; a choice outside [0, Nl) pastes an empty mask.  No atomics, no synchronisation, nothing allocated; the same input
+ * gives the same bytes on every run. */
+typedef struct umr_cp_pair {
+    const uint8_t* l_image;   /* [3,Hl,Wl] u8 */
+    const uint8_t* l_masks;   /* [Nl,Hl,Wl] u8 / bool */
+    const float* l_boxes;     /* [Nl,4] f32 (read when Nu == 0) */
+    const uint8_t* u_image;   /* [3,Hu,Wu] u8 */
+    const uint8_t* u_masks;   /* [Nu,Hu,Wu] u8 / bool; may be NULL when Nu == 0 */
+    uint8_t* out_image;       /* [3,Hu,Wu] u8 */
+    uint8_t* out_masks;       /* [Nu + nc,Hu,Wu] u8 */
+    int64_t word_off, inter_off, row_off, choice_off;
+    int32_t Hl, Wl, Nl, Hu, Wu, Nu, nc, h_new, w_new, h_shift, w_shift;
+    float rh, rw;             /* (float)Hl / (float)h_new, (float)Wl / (float)w_new */
+    float sx, sy;             /* box scale: Wu / Wl * ratio, Hu / Hl * ratio, rounded to float32 */
+    int32_t reserved;
+} umr_cp_pair;
+int64_t umr_copy_paste_workspace(int64_t total_words, int64_t total_inter);
+int umr_copy_paste(const umr_cp_pair* pairs, int P, const int32_t* choice, int64_t total_choice, int64_t total_words,
+                   int64_t total_inter, int64_t total_rows, int64_t max_words_per_mask, int max_nc, int max_nu, int phases,
+                   int32_t* stats, float* boxes, void* workspace, int64_t workspace_bytes, umr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -54,6 +54,14 @@ class RaggedSrc(ctypes.Structure):   # umr_ragged_src
     _fields_ = [("f32", _vp), ("u8", _vp), ("H", _i32), ("W", _i32)]
 
 
+class CpPair(ctypes.Structure):   # umr_cp_pair
+    _fields_ = [("l_image", _vp), ("l_masks", _vp), ("l_boxes", _vp), ("u_image", _vp), ("u_masks", _vp), ("out_image", _vp), ("out_masks", _vp),
+                ("word_off", _i64), ("inter_off", _i64), ("row_off", _i64), ("choice_off", _i64),
+                ("Hl", _i32), ("Wl", _i32), ("Nl", _i32), ("Hu", _i32), ("Wu", _i32), ("Nu", _i32), ("nc", _i32), ("h_new", _i32), ("w_new", _i32),
+                ("h_shift", _i32), ("w_shift", _i32), ("rh", ctypes.c_float), ("rw", ctypes.c_float), ("sx", ctypes.c_float), ("sy", ctypes.c_float),
+                ("reserved", _i32)]
+
+
 class PermEntry(ctypes.Structure):   # umr_perm_entry
     _fields_ = [("src", _vp), ("dst", _vp), ("d", _i32 * 4), ("sstride", _i64 * 4), ("soff", _i64), ("dtype_in", _i32), ("dtype_out", _i32),
                 ("blk_start", _i64), ("e", _i32 * 4), ("ord", _i32 * 4), ("rowlen", _i64)]
@@ -150,6 +158,8 @@ _SIGS = {
     "umr_box_iou": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _vp, _vp],
     "umr_coco_match": [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
                        _vp],
+    "umr_copy_paste_workspace": [_i64, _i64],
+    "umr_copy_paste": [_vp, _i32, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp],
     "umr_mask_components": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
     "umr_nms_workspace": [_i32],
     "umr_nms": [_vp, _vp, _i32, _f32, _vp, _i64, _vp, _vp, _vp],
@@ -201,7 +211,7 @@ def lib():
                    "umr_linear_head_bwd_weight_workspace", "umr_linear_head_shift9_workspace", "umr_label_synthesis_workspace", "umr_attention_bwd_workspace",
                    "umr_distance_transform_workspace", "umr_gemm_nt_workspace", "umr_gemm_nt_x3_workspace", "umr_nms_workspace",
                    "umr_bn_train_workspace", "umr_bg_square_workspace", "umr_rle_decode_workspace", "umr_mask_iou_workspace",
-                   "umr_poly_rle_workspace"):
+                   "umr_poly_rle_workspace", "umr_copy_paste_workspace"):
             getattr(_lib, fn).restype = ctypes.c_int64
     return _lib
 
