@@ -667,6 +667,46 @@ int umr_copy_paste(const umr_cp_pair* pairs, int P, const int32_t* choice, int64
                    int64_t total_inter, int64_t total_rows, int64_t max_words_per_mask, int max_nc, int max_nu, int phases,
                    int32_t* stats, float* boxes, void* workspace, int64_t workspace_bytes, umr_stream_t stream);
 
+/* ---- mask-head targets and the score-weighted mask loss of the detector (cad/modeling/roi_heads/roi_heads.py:963-1045,
+ * mask_rcnn_loss_weighted, "soft targets"; csrc/mask_loss.hip) -----------------------------------------------------------------------
+ * R proposals in image order over a table of n_images entries; proposal r belongs to the last entry with first <= r and is its
+ * proposal j = r - first: box boxes[j] (XYXY), mask index[j] (int32, or int64 with index64 != 0; NULL = the identity j) of the entry's G
+ * masks -- the reference gathers one full frame per proposal first (gt_masks[matched_idxs]), here the kernel reads the mask in place.
+ * Target [M,M] of a proposal: Detectron2's BitMasks.crop_and_resize = torchvision roi_align(spatial_scale 1, sampling_ratio 0,
+ * aligned) of the 0 / 1 mask (non-zero byte = 1), then >= 0.5, in float32 and in torchvision's operation order (csrc/mask_loss.hip
+ * writes it out).  A box that is empty (x2 <= x1 or y2 <= y1) has no samples and a zero target.
+ * mask_targets: targets u8 [R,M,M] (0 / 1) only.
+ * mask_loss: logits [R,C,M,M] (UMR_F32 / UMR_BF16, contiguous); the logit x of proposal r is channel 0 (C == 1) or gt_classes[r];
+ *   loss[0] = mean over R*M*M of weights[r] * ((1 - t) * x + max(-x, 0) + log1p(exp(-|x|))) as float32 (terms in float32, sums in
+ *   double; weights == NULL: ones; R == 0: 0); grad [R,C,M,M] in the logits' type = weights[r] * (sigmoid(x) - t) / (R*M*M) in that
+ *   channel, 0 in the others; counts int64 [5] = elements with (x > 0) != t, with t, with both (x > 0) and !t, with !(x > 0) and t,
+ *   and the number of BAD proposals; targets: optional u8 [R,M,M].
+ * A bad proposal -- mask index outside [0, G), a box coordinate that is not finite or beyond +-2^20 -- gets a zero target and is
+ *   counted; nothing of it is read out of bounds.  A class outside [0, C) is counted too and adds no loss, no count and no gradient.
+ * max_h, max_w: the largest H and W in the table; they size the kernel's LDS tables, 16 * (max_h + max_w) + 32 * M + 328 bytes, at
+ *   most 160 KiB (else UMR_ERR_INVALID); 1 <= M <= 512.  Work per proposal is at most (2 * (H + 4) + M) * (2 * (W + 4) + M) samples
+ *   whatever its box; a proposal of more than 65536 samples is shared by ceil(M * M / 256) workgroups, whole rows of bins each.
+ *   workspace >= mask_loss_workspace(R, M) bytes (one 32-byte partial per workgroup; -1 for a negative R or an M outside [1, 512]),
+ *   8-byte aligned.
+ * phases: a mask of 1 = targets, loss terms, gradient and the partials, 2 = the finishing sum; a caller that times the parts
+ *   runs 1, 2 on the same buffers, everyone else passes 3.  No atomics, no synchronisation, nothing allocated; the same input gives
+ *   the same bytes on every run. */
+typedef struct umr_ml_image {
+    const uint8_t* masks;     /* [G,H,W] u8 / bool */
+    const float* boxes;       /* [R_i,4] f32 XYXY */
+    const void* index;        /* [R_i] int32 / int64, or NULL */
+    int32_t H, W, G;
+    int32_t first;            /* the image's first proposal: the sum of the R_i before it */
+    int32_t R;                /* R_i */
+    int32_t index64;
+} umr_ml_image;
+int64_t umr_mask_loss_workspace(int64_t R, int M);
+int umr_mask_targets(const umr_ml_image* images, int n_images, int64_t R, int M, int max_h, int max_w, uint8_t* targets,
+                     umr_stream_t stream);
+int umr_mask_loss(const umr_ml_image* images, int n_images, int64_t R, int C, int M, int max_h, int max_w, const void* logits,
+                  int dtype, const int64_t* gt_classes, const float* weights, int phases, uint8_t* targets, void* grad,
+                  float* loss, int64_t* counts, void* workspace, int64_t workspace_bytes, umr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
