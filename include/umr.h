@@ -707,6 +707,68 @@ int umr_mask_loss(const umr_ml_image* images, int n_images, int64_t R, int C, in
                   int dtype, const int64_t* gt_classes, const float* weights, int phases, uint8_t* targets, void* grad,
                   float* loss, int64_t* counts, void* workspace, int64_t workspace_bytes, umr_stream_t stream);
 
+/* ---- the box branch of the detector's cascade ROI heads (cad/modeling/roi_heads/custom_cascade_rcnn.py:166-357, fast_rcnn.py:94-121,
+ * 329-390, 462-514, 574-598, cad/structures/boxes.py, cad/modeling/box_regression.py; csrc/box_loss.hip) ---------------------------------
+ * R proposals in image order over a table of n_images entries, cut into chunks of 256 rows per image: entry k owns the chunks
+ * [chunk_first, chunk_first + ceil(R_k / 256)) and n_chunks is their total.  Boxes are float32 XYXY.  What gt_* point to depends on the
+ * entry point: box_match reads the image's G ground truths ([G,4], [G], [G]); box_loss and box_drop_weights read the MATCHED fields,
+ * one row per proposal ([R_k,4], [R_k], [R_k]; box_drop_weights reads gt_boxes only); box_decode reads boxes, height and width only.
+ * IoU is Detectron2's pairwise_iou in float32, every operation rounded on its own and the division correctly rounded.
+ * box_match (Matcher([t], [0, 1], allow_low_quality_matches=False)): per row matched_vals = the maximum IoU over the image's ground truths,
+ *   matched_idxs = the lowest index that attains it, label = matched_vals >= t; gt_classes = the matched class or num_classes, gt_boxes /
+ *   gt_scores gathered by matched_idxs on every row.  G == 0: index 0, value 0, background, zero box and score.  A proposal with a
+ *   non-finite coordinate is bad: index 0, value 0, background.  A NaN IoU caused by a ground truth never wins the maximum (torch's max
+ *   would hand it on); a row whose every IoU is NaN is background with index 0 and value 0, and is not counted.  counts int32 [3, n_images], ZEROED BY THE CALLER: foreground,
+ *   background and bad rows per image (integer atomics, one per workgroup).
+ * box_decode: Box2BoxTransform.apply_deltas(deltas, boxes) with weights (wx, wy, ww, wh), Boxes.clip to (height, width) and, when
+ *   training != 0, the rows with width > 0 and height > 0 only: boxes [R,4] compacted in order, image after image (tail undefined),
+ *   keep u8 [R], counts int32 [n_images].  workspace >= box_decode_workspace(R, n_chunks) bytes, 4-byte aligned.
+ * box_apply_deltas / box_get_deltas: the two transforms as element-wise ops over n rows.
+ * box_drop_weights: weights [R] of the reference's drop-loss block: the ground-truth set of image k is the first n_k rows of its matched
+ *   gt_boxes, n_k = the number of distinct rows among the first min(100, R_k); weight = !(max IoU of the row's decoded, unclipped
+ *   prediction with that set <= iou_thresh); then row r takes 1 where is_single_object[r / (R / n_images)] == 1 (float32
+ *   [n_images] or NULL; by POSITION, as the reference indexes it).
+ * box_loss (FastRCNNOutputLayers.losses): scores [R,K1], deltas [R,4] (UMR_F32 / UMR_BF16), K1 == num_classes + 1.  drop_mode 0: weights
+ *   of one, 1: weights_in [R], 2: the rule above.  loss_cls[0] = mean over R of w_r * CE_r, CE against the soft targets (fg, 1 - fg), fg =
+ *   gt_scores or 0 on background rows (soft_targets != 0, K1 == 2), or against gt_classes; loss_box_reg[0] = sum over the rows with
+ *   0 <= class < num_classes of smooth_l1(deltas - get_deltas(box, gt_box), beta) (* gt_scores with soft targets) / max(R, 1); terms in
+ *   float32, sums in double.  grad_scores = w (softmax - target) / R and grad_deltas = smooth_l1' * score / R in the inputs' type;
+ *   weights [R] = the weights used; counters int64 [7] = rows, foreground rows, argmax == class, foreground with argmax == class,
+ *   foreground predicted background, rows of weight 0, bad rows (a foreground row whose proposal or ground-truth extent is not positive
+ *   or finite: no box term; a class no column stands for without soft targets: no term at all).
+ *   workspace >= box_loss_workspace(n_chunks) bytes (one 48-byte partial per workgroup), 8-byte aligned.  phases as in mask_loss.
+ * No float atomics, no synchronisation, nothing allocated; the same input gives the same bytes on every run. */
+typedef struct umr_bl_image {
+    const float* boxes;          /* [R_k,4] proposals */
+    const float* gt_boxes;
+    const int64_t* gt_classes;
+    const float* gt_scores;
+    int32_t first;               /* the image's first proposal: the sum of the R before it */
+    int32_t R, G;
+    int32_t chunk_first;         /* the image's first chunk: the sum of ceil(R / 256) before it */
+    float height, width;         /* the frame, for the clip */
+} umr_bl_image;
+int64_t umr_box_loss_workspace(int64_t n_chunks);
+int64_t umr_box_decode_workspace(int64_t R, int64_t n_chunks);
+int umr_box_match(const umr_bl_image* images, int n_images, int64_t R, int64_t n_chunks, float iou_threshold, int64_t num_classes,
+                  int64_t* matched_idxs, float* matched_vals, int64_t* gt_classes, float* gt_boxes, float* gt_scores, int32_t* counts,
+                  umr_stream_t stream);
+int umr_box_decode(const umr_bl_image* images, int n_images, int64_t R, int64_t n_chunks, const void* deltas, int dtype, float wx, float wy,
+                   float ww, float wh, int training, float* boxes, uint8_t* keep, int32_t* counts, void* workspace,
+                   int64_t workspace_bytes, umr_stream_t stream);
+int umr_box_apply_deltas(const void* deltas, int dtype, const float* boxes, int64_t n, float wx, float wy, float ww, float wh, float* out,
+                         umr_stream_t stream);
+int umr_box_get_deltas(const float* src, const float* target, int64_t n, float wx, float wy, float ww, float wh, float* out,
+                       umr_stream_t stream);
+int umr_box_drop_weights(const umr_bl_image* images, int n_images, int64_t R, int64_t n_chunks, const void* deltas, int dtype, float wx,
+                         float wy, float ww, float wh, float iou_thresh, const float* is_single_object, float* weights,
+                         umr_stream_t stream);
+int umr_box_loss(const umr_bl_image* images, int n_images, int64_t R, int64_t n_chunks, int K1, int64_t num_classes, const void* scores,
+                 const void* deltas, int dtype, float wx, float wy, float ww, float wh, float smooth_l1_beta, int soft_targets,
+                 int drop_mode, float iou_thresh, const float* weights_in, const float* is_single_object, int phases, float* weights,
+                 void* grad_scores, void* grad_deltas, float* loss_cls, float* loss_box_reg, int64_t* counters, void* workspace,
+                 int64_t workspace_bytes, umr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,11 @@ class MlImage(ctypes.Structure):   # umr_ml_image
                 ("index64", _i32)]
 
 
+class BlImage(ctypes.Structure):   # umr_bl_image
+    _fields_ = [("boxes", _vp), ("gt_boxes", _vp), ("gt_classes", _vp), ("gt_scores", _vp), ("first", _i32), ("R", _i32), ("G", _i32),
+                ("chunk_first", _i32), ("height", ctypes.c_float), ("width", ctypes.c_float)]
+
+
 class PermEntry(ctypes.Structure):   # umr_perm_entry
     _fields_ = [("src", _vp), ("dst", _vp), ("d", _i32 * 4), ("sstride", _i64 * 4), ("soff", _i64), ("dtype_in", _i32), ("dtype_out", _i32),
                 ("blk_start", _i64), ("e", _i32 * 4), ("ord", _i32 * 4), ("rowlen", _i64)]
@@ -168,6 +173,15 @@ _SIGS = {
     "umr_mask_loss_workspace": [_i64, _i32],
     "umr_mask_targets": [_vp, _i32, _i64, _i32, _i32, _i32, _vp, _vp],
     "umr_mask_loss": [_vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+    "umr_box_loss_workspace": [_i64],
+    "umr_box_decode_workspace": [_i64, _i64],
+    "umr_box_match": [_vp, _i32, _i64, _i64, _f32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
+    "umr_box_decode": [_vp, _i32, _i64, _i64, _vp, _i32, _f32, _f32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _i64, _vp],
+    "umr_box_apply_deltas": [_vp, _i32, _vp, _i64, _f32, _f32, _f32, _f32, _vp, _vp],
+    "umr_box_get_deltas": [_vp, _vp, _i64, _f32, _f32, _f32, _f32, _vp, _vp],
+    "umr_box_drop_weights": [_vp, _i32, _i64, _i64, _vp, _i32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp],
+    "umr_box_loss": [_vp, _i32, _i64, _i64, _i32, _i64, _vp, _vp, _i32, _f32, _f32, _f32, _f32, _f32, _i32, _i32, _f32, _vp, _vp, _i32, _vp, _vp,
+                     _vp, _vp, _vp, _vp, _vp, _i64, _vp],
     "umr_mask_components": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
     "umr_nms_workspace": [_i32],
     "umr_nms": [_vp, _vp, _i32, _f32, _vp, _i64, _vp, _vp, _vp],
@@ -219,7 +233,8 @@ def lib():
                    "umr_linear_head_bwd_weight_workspace", "umr_linear_head_shift9_workspace", "umr_label_synthesis_workspace", "umr_attention_bwd_workspace",
                    "umr_distance_transform_workspace", "umr_gemm_nt_workspace", "umr_gemm_nt_x3_workspace", "umr_nms_workspace",
                    "umr_bn_train_workspace", "umr_bg_square_workspace", "umr_rle_decode_workspace", "umr_mask_iou_workspace",
-                   "umr_poly_rle_workspace", "umr_copy_paste_workspace", "umr_mask_loss_workspace"):
+                   "umr_poly_rle_workspace", "umr_copy_paste_workspace", "umr_mask_loss_workspace", "umr_box_loss_workspace",
+                   "umr_box_decode_workspace"):
             getattr(_lib, fn).restype = ctypes.c_int64
     return _lib
 
