@@ -498,3 +498,35 @@ def test_hand_worked_cases_on_the_device():
         got = B.droploss_weights(torch.zeros(R, 4, device=dev), [far(n) for n in rows], W4, 0.01,
                                  None if single is None else torch.tensor(single, device=dev))
         assert got.tolist() == want, (rows, single)
+
+
+def test_more_than_256_chunks_reach_the_strided_part_of_the_finishing_sum():
+    """257 images of one proposal and one matched ground truth each: every image starts a chunk of its own, so the finishing launch adds
+    257 partials and its thread 0 adds partial 0 and partial 256.  Weights, scores and a few background rows make every partial differ."""
+    from unmore_amd import box_loss as B
+    dev, N = _dev(), 257
+    rng = np.random.RandomState(257)
+    xy, wh = rng.uniform(0, 80, (N, 2)), rng.uniform(8, 40, (N, 2))
+    gb = np.concatenate([xy, xy + wh], axis=1).astype(np.float32)
+    pb = (gb + rng.uniform(-0.2, 0.2, (N, 4)) * np.tile(wh, 2)).astype(np.float32)
+    gc = (rng.uniform(size=N) < 0.25).astype(np.int64)                 # 1 == num_classes: background
+    gs, w = rng.uniform(0.2, 1.0, N).astype(np.float32), rng.uniform(0.0, 2.0, N).astype(np.float32)
+    scores = (rng.standard_normal((N, 2)) * 3).astype(np.float32)
+    deltas = (rng.standard_normal((N, 4)) * np.array(W4) * 0.05).astype(np.float32)
+    lc, lb, _, _, counters = losses_reference(scores, deltas, pb, gb, gc, gs, w, W4)
+    items = [{"proposal_boxes": _t(pb[k:k + 1], dev), "gt_boxes": _t(gb[k:k + 1], dev), "gt_classes": _t(gc[k:k + 1], dev),
+              "gt_scores": _t(gs[k:k + 1], dev)} for k in range(N)]
+    runs = []
+    for _ in range(2):
+        s, d = _t(scores, dev).requires_grad_(True), _t(deltas, dev).requires_grad_(True)
+        st = {}
+        out = B.fast_rcnn_losses(s, d, items, box2box_weights=W4, weights=_t(w, dev), stats=st)
+        (out["loss_cls"] + out["loss_box_reg"]).backward()
+        runs.append((out["loss_cls"].detach(), out["loss_box_reg"].detach(), st["counters"], s.grad, d.grad))
+    got_c, got_b = float(runs[0][0]), float(runs[0][1])
+    print(f"loss_cls {got_c!r} (float64 {lc!r}), loss_box_reg {got_b!r} (float64 {lb!r})")
+    assert abs(got_c - lc) <= 1e-5 * max(1, abs(lc)) and abs(got_b - lb) <= 1e-5 * max(1, abs(lb))
+    assert runs[0][2].tolist() == counters and counters[0] == N and 0 < counters[1] < N and counters[6] == 0
+    assert torch.equal(runs[0][0].view(torch.int32), runs[1][0].view(torch.int32)) and torch.equal(runs[0][1].view(torch.int32), runs[1][1].view(torch.int32))
+    assert torch.equal(runs[0][2], runs[1][2])
+    assert torch.equal(runs[0][3].view(torch.int32), runs[1][3].view(torch.int32)) and torch.equal(runs[0][4].view(torch.int32), runs[1][4].view(torch.int32))

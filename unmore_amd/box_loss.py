@@ -6,27 +6,19 @@ reference's several dozen small launches and its host reads: `match_and_label` (
 _create_proposals_from_boxes).  `apply_deltas`, `get_deltas` and `droploss_weights` expose the pieces.  The matcher's index comes
 back as `mask_index`, which is what mask_loss.mask_rcnn_loss_weighted reads the masks through.  No CPU fallback:
 tests/box_loss_common.py restates the method in NumPy and torch CPU ops (csrc/box_loss.hip writes the arithmetic out)."""
-import ctypes
 import math
 
-import numpy as np
 import torch
+
+from . import _lib as L
+from . import _tables as T
+from .ops import _p, _stream
 
 CHUNK = 256                  # proposals per workgroup (csrc/box_loss.hip: BL_THREADS)
 GT_TILE = 256                # ground truths staged in LDS at a time (BL_GT_TILE)
 UNIQUE_ROWS = 100            # the reference's gt_boxes.tensor[:100]
 SCALE_CLAMP = math.log(1000.0 / 16)
 COUNTERS = ("rows", "fg", "accurate", "fg_accurate", "false_negative", "dropped", "bad")
-
-
-def _tensor(v):
-    return getattr(v, "tensor", v)                       # Detectron2's Boxes, or the tensor itself
-
-
-def _getter(item):
-    if isinstance(item, dict):
-        return item.get
-    return lambda name: getattr(item, name, None)
 
 
 def _check_boxes(b, what, name):
@@ -47,14 +39,7 @@ def _check_vector(v, n, what, name, integer):
 
 
 def _device(tensors, what):
-    """the one device of `tensors`: ValueError when they differ, RuntimeError when it is not the GPU"""
-    devs = {t.device for t in tensors}
-    if len(devs) > 1:
-        raise ValueError(f"box_loss: every tensor must be on the same device, got {sorted(str(d) for d in devs)}")
-    dev = devs.pop()
-    if dev.type != "cuda":
-        raise RuntimeError(f"unmore_amd.box_loss.{what} runs on the MI355X only (no CPU fallback); tests/box_loss_common.py restates it on the host")
-    return dev
+    return T.one_device(tensors, "box_loss", what)
 
 
 def _weights4(w):
@@ -67,11 +52,6 @@ def _weights4(w):
     return w
 
 
-def _dtype_code(t):
-    from . import _lib as L
-    return L.BF16 if t.dtype == torch.bfloat16 else L.F32
-
-
 def _chunks(n):
     return (n + CHUNK - 1) // CHUNK
 
@@ -79,7 +59,6 @@ def _chunks(n):
 def _upload_table(images, dev):
     """one umr_bl_image per image -- (boxes, gt_boxes, gt_classes, gt_scores, (height, width)), None where the call does not read it --
     in one host-to-device copy: (device buffer, what the table points into, R, number of chunks)"""
-    from . import _lib as L
     tab = (L.BlImage * max(len(images), 1))()
     hold, first, chunk = [], 0, 0
     for k, (boxes, gtb, gtc, gts, size) in enumerate(images):
@@ -93,20 +72,7 @@ def _upload_table(images, dev):
         e.height, e.width = (0.0, 0.0) if size is None else (float(size[0]), float(size[1]))
         first += n
         chunk += _chunks(n)
-    host = np.frombuffer(tab, dtype=np.uint8)[:ctypes.sizeof(L.BlImage) * len(images)].copy()
-    return torch.from_numpy(host).to(dev), hold, first, chunk
-
-
-def _launch(call, name, _phase_ms):
-    """run the launches of `call`; with a dict (tools/box_loss_bench.py), between device events, their time added under `name`"""
-    if _phase_ms is None:
-        return call()
-    ev = [torch.cuda.Event(enable_timing=True) for _ in range(2)]
-    ev[0].record()
-    call()
-    ev[1].record()
-    ev[1].synchronize()
-    _phase_ms[name] = _phase_ms.get(name, 0.0) + ev[0].elapsed_time(ev[1])
+    return T.upload(tab, len(images), dev)[0], hold, first, chunk
 
 
 # ------------------------------------------------------------------------------------------------------------------ match and label
@@ -149,10 +115,10 @@ def match_and_label(proposals, targets, iou_threshold, num_classes=1, *, stats=N
         raise ValueError("box_loss: the IoU threshold is NaN")
     images, masks, tensors = [], [], []
     for k, (p, g) in enumerate(zip(proposals, targets)):
-        boxes = _tensor(p if isinstance(p, torch.Tensor) else _getter(p)("proposal_boxes"))
+        boxes = T.unwrap(p if isinstance(p, torch.Tensor) else T.getter(p)("proposal_boxes"))
         _check_boxes(boxes, f"proposals[{k}]", "proposal_boxes")
-        get = _getter(g)
-        gtb, gtc, gts = _tensor(get("gt_boxes")), get("gt_classes"), get("gt_scores")
+        get = T.getter(g)
+        gtb, gtc, gts = T.unwrap(get("gt_boxes")), get("gt_classes"), get("gt_scores")
         n = _check_boxes(gtb, f"targets[{k}]", "gt_boxes")
         _check_vector(gtc, n, f"targets[{k}]", "gt_classes", True)
         _check_vector(gts, n, f"targets[{k}]", "gt_scores", False)
@@ -163,8 +129,6 @@ def match_and_label(proposals, targets, iou_threshold, num_classes=1, *, stats=N
     if R >= 1 << 31:
         raise ValueError("box_loss: 2^31 proposals or more")
     dev = _device(tensors, "match_and_label")
-    from . import _lib as L
-    from .ops import _stream
     N = len(images)
     with torch.cuda.device(dev):
         images = [(b, gb, gc.to(torch.int64), gs, s) for b, gb, gc, gs, s in images]
@@ -174,11 +138,9 @@ def match_and_label(proposals, targets, iou_threshold, num_classes=1, *, stats=N
         counts = torch.zeros((3, N), dtype=torch.int32, device=dev)
         if R:
             buf, hold, _, n_chunks = _upload_table(images, dev)
-            vp = ctypes.c_void_p
-            _launch(lambda: L.check(L.lib().umr_box_match(vp(buf.data_ptr()), N, R, n_chunks, t, num_classes, vp(idx.data_ptr()),
-                                                          vp(vals.data_ptr()), vp(classes.data_ptr()), vp(boxes.data_ptr()),
-                                                          vp(scores.data_ptr()), vp(counts.data_ptr()), _stream()), "umr_box_match"),
-                    "match", _phase_ms)
+            T.timed(lambda _: L.check(L.lib().umr_box_match(_p(buf), N, R, n_chunks, t, num_classes, _p(idx), _p(vals), _p(classes), _p(boxes),
+                                                            _p(scores), _p(counts), _stream()), "umr_box_match"),
+                    (("match", 1),), _phase_ms)                                # tools/box_loss_bench.py times the launch
             del hold
     sizes = [int(im[0].shape[0]) for im in images]
     out = []
@@ -209,45 +171,38 @@ def _check_deltas(d, n, name="proposal_deltas"):
 def apply_deltas(deltas, boxes, weights):
     """Detectron2's Box2BoxTransform(weights).apply_deltas(deltas, boxes), class-agnostic, in float32: deltas float32 or bfloat16 [n,4],
     boxes float32 [n,4] XYXY -> float32 [n,4].  dw and dh are clamped at log(1000 / 16); expf, not a fast intrinsic."""
-    boxes = _tensor(boxes)
+    boxes = T.unwrap(boxes)
     n = _check_boxes(boxes, "apply_deltas", "boxes")
     _check_deltas(deltas, n, "deltas")
     w = _weights4(weights)
     dev = _device([deltas, boxes], "apply_deltas")
-    from . import _lib as L
-    from .ops import _stream
     with torch.cuda.device(dev):
         d, b = deltas.detach().contiguous(), boxes.contiguous()
         out = torch.empty((n, 4), dtype=torch.float32, device=dev)
-        vp = ctypes.c_void_p
-        L.check(L.lib().umr_box_apply_deltas(vp(d.data_ptr()), _dtype_code(d), vp(b.data_ptr()), n, *w, vp(out.data_ptr()), _stream()),
-                "umr_box_apply_deltas")
+        L.check(L.lib().umr_box_apply_deltas(_p(d), T.dtype_code(d), _p(b), n, *w, _p(out), _stream()), "umr_box_apply_deltas")
     return out
 
 
 def get_deltas(src_boxes, target_boxes, weights):
     """Detectron2's Box2BoxTransform(weights).get_deltas(src_boxes, target_boxes) in float32: two float32 [n,4] -> float32 [n,4].
     Detectron2 asserts positive source widths; this plain op returns what the arithmetic gives (inf / NaN there)."""
-    src, tgt = _tensor(src_boxes), _tensor(target_boxes)
+    src, tgt = T.unwrap(src_boxes), T.unwrap(target_boxes)
     n = _check_boxes(src, "get_deltas", "src_boxes")
     if _check_boxes(tgt, "get_deltas", "target_boxes") != n:
         raise ValueError(f"box_loss: get_deltas: {n} source boxes for {int(tgt.shape[0])} target boxes")
     w = _weights4(weights)
     dev = _device([src, tgt], "get_deltas")
-    from . import _lib as L
-    from .ops import _stream
     with torch.cuda.device(dev):
         s, t = src.contiguous(), tgt.contiguous()
         out = torch.empty((n, 4), dtype=torch.float32, device=dev)
-        vp = ctypes.c_void_p
-        L.check(L.lib().umr_box_get_deltas(vp(s.data_ptr()), vp(t.data_ptr()), n, *w, vp(out.data_ptr()), _stream()), "umr_box_get_deltas")
+        L.check(L.lib().umr_box_get_deltas(_p(s), _p(t), n, *w, _p(out), _stream()), "umr_box_get_deltas")
     return out
 
 
 def _proposal_boxes(proposals):
     out = []
     for k, p in enumerate(proposals):
-        b = _tensor(p if isinstance(p, torch.Tensor) else _getter(p)("proposal_boxes"))
+        b = T.unwrap(p if isinstance(p, torch.Tensor) else T.getter(p)("proposal_boxes"))
         _check_boxes(b, f"proposals[{k}]", "proposal_boxes")
         out.append(b)
     return out
@@ -271,8 +226,6 @@ def next_stage_proposals(proposal_deltas, proposals, box2box_weights, image_size
     _check_deltas(proposal_deltas, R)
     w = _weights4(box2box_weights)
     dev = _device([proposal_deltas] + boxes, "next_stage_proposals")
-    from . import _lib as L
-    from .ops import _stream
     N = len(boxes)
     with torch.cuda.device(dev):
         out = torch.empty((R, 4), dtype=torch.float32, device=dev)
@@ -283,11 +236,9 @@ def next_stage_proposals(proposal_deltas, proposals, box2box_weights, image_size
             buf, hold, _, n_chunks = _upload_table([(b, None, None, None, s) for b, s in zip(boxes, sizes)], dev)
             nbytes = L.lib().umr_box_decode_workspace(R, n_chunks)
             ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
-            vp = ctypes.c_void_p
-            _launch(lambda: L.check(L.lib().umr_box_decode(vp(buf.data_ptr()), N, R, n_chunks, vp(d.data_ptr()), _dtype_code(d), *w,
-                                                           int(bool(training)), vp(out.data_ptr()), vp(keep.data_ptr()), vp(counts.data_ptr()),
-                                                           vp(ws.data_ptr()), nbytes, _stream()), "umr_box_decode"),
-                    "decode", _phase_ms)
+            T.timed(lambda _: L.check(L.lib().umr_box_decode(_p(buf), N, R, n_chunks, _p(d), T.dtype_code(d), *w, int(bool(training)), _p(out),
+                                                             _p(keep), _p(counts), _p(ws), nbytes, _stream()), "umr_box_decode"),
+                    (("decode", 1),), _phase_ms)
             del hold
     return out, keep.view(torch.bool), counts
 
@@ -302,8 +253,8 @@ def split_proposals(boxes, counts):
 def _loss_images(proposals, need_classes, need_scores):
     images, tensors = [], []
     for k, p in enumerate(proposals):
-        get = _getter(p)
-        boxes, gtb = _tensor(get("proposal_boxes")), _tensor(get("gt_boxes"))
+        get = T.getter(p)
+        boxes, gtb = T.unwrap(get("proposal_boxes")), T.unwrap(get("gt_boxes"))
         n = _check_boxes(boxes, f"proposals[{k}]", "proposal_boxes")
         if _check_boxes(gtb, f"proposals[{k}]", "gt_boxes") != n:
             raise ValueError(f"box_loss: proposals[{k}]: {int(gtb.shape[0])} matched gt_boxes for {n} proposals")
@@ -355,18 +306,14 @@ def droploss_weights(proposal_deltas, proposals, box2box_weights, iou_thresh, is
     w = _weights4(box2box_weights)
     thresh, single = _check_droploss((iou_thresh, is_single_object), len(images))
     dev = _device([proposal_deltas] + tensors + ([] if single is None else [single]), "droploss_weights")
-    from . import _lib as L
-    from .ops import _stream
     with torch.cuda.device(dev):
         out = torch.empty(R, dtype=torch.float32, device=dev)
         if R:
             d = proposal_deltas.detach().contiguous()
             s = None if single is None else single.to(torch.float32).contiguous()
             buf, hold, _, n_chunks = _upload_table(images, dev)
-            vp = ctypes.c_void_p
-            L.check(L.lib().umr_box_drop_weights(vp(buf.data_ptr()), len(images), R, n_chunks, vp(d.data_ptr()), _dtype_code(d), *w, thresh,
-                                                 None if s is None else vp(s.data_ptr()), vp(out.data_ptr()), _stream()),
-                    "umr_box_drop_weights")
+            L.check(L.lib().umr_box_drop_weights(_p(buf), len(images), R, n_chunks, _p(d), T.dtype_code(d), *w, thresh, _p(s), _p(out),
+                                                 _stream()), "umr_box_drop_weights")
             del hold
     return out
 
@@ -454,8 +401,6 @@ def fast_rcnn_losses(scores, proposal_deltas, proposals, *, box2box_weights, num
     else:
         lw = {k: float(loss_weight) for k in ("loss_cls", "loss_box_reg")}
     dev = _device([x, proposal_deltas] + tensors + [t for t in (weights, single) if t is not None], "fast_rcnn_losses")
-    from . import _lib as L
-    from .ops import _stream
     mode = 2 if droploss is not None else (1 if weights is not None else 0)
     N = len(images)
     got = {}
@@ -475,26 +420,12 @@ def fast_rcnn_losses(scores, proposal_deltas, proposals, *, box2box_weights, num
             ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
             w_in = None if weights is None else weights.detach().contiguous()
             sg = None if single is None else single.to(torch.float32).contiguous()
-            vp = ctypes.c_void_p
 
             def launch(phases):
-                L.check(L.lib().umr_box_loss(vp(buf.data_ptr()), N, R, n_chunks, K1, num_classes, vp(s.data_ptr()), vp(d.data_ptr()),
-                                             _dtype_code(s), *bw, beta, int(bool(use_soft_targets)), mode, thresh,
-                                             None if w_in is None else vp(w_in.data_ptr()), None if sg is None else vp(sg.data_ptr()), phases,
-                                             vp(w_out.data_ptr()), vp(g_s.data_ptr()), vp(g_d.data_ptr()), vp(loss_cls.data_ptr()),
-                                             vp(loss_box.data_ptr()), vp(counters.data_ptr()), vp(ws.data_ptr()), nbytes, _stream()),
-                        "umr_box_loss")
-            if _phase_ms is None:
-                launch(3)
-            else:                                                              # tools/box_loss_bench.py: the two parts between events
-                ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-                for i, ph in enumerate((1, 2)):
-                    ev[i].record()
-                    launch(ph)
-                ev[2].record()
-                ev[2].synchronize()
-                for name, i in (("loss_main", 0), ("loss_finish", 1)):
-                    _phase_ms[name] = _phase_ms.get(name, 0.0) + ev[i].elapsed_time(ev[i + 1])
+                L.check(L.lib().umr_box_loss(_p(buf), N, R, n_chunks, K1, num_classes, _p(s), _p(d), T.dtype_code(s), *bw, beta,
+                                             int(bool(use_soft_targets)), mode, thresh, _p(w_in), _p(sg), phases, _p(w_out), _p(g_s), _p(g_d),
+                                             _p(loss_cls), _p(loss_box), _p(counters), _p(ws), nbytes, _stream()), "umr_box_loss")
+            T.timed(launch, (("loss_main", 1), ("loss_finish", 2)), _phase_ms)
             del hold
         return loss_cls, loss_box, g_s, g_d
 

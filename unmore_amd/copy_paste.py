@@ -3,7 +3,6 @@ CustomSimpleTrainer.copy_and_paste, which the reference's recipe turns on for ev
 cascade_mask_rcnn_R_50_FPN.yaml:3-8,58).  `draw_params` makes the reference's random draws on the host, from the reference's two random
 streams and in its order; `copy_and_paste` runs a whole batch of pairs through one sequence of launches (csrc/copy_paste.hip).  No CPU
 fallback: tests/copy_paste_common.py restates the method in torch CPU ops."""
-import ctypes
 import random
 
 import numpy as np
@@ -79,12 +78,6 @@ def _check_params(prm, p, Nl, Hu, Wu):
     return choice, ratio, h_new, w_new, h_shift, w_shift
 
 
-def _u8(t):
-    import torch
-    t = t.contiguous()
-    return t.view(torch.uint8) if t.dtype == torch.bool else t
-
-
 def copy_and_paste(labeled, unlabeled, params=None, *, rate=1.0, random_num=True, min_ratio=0.3, max_ratio=1.0, _phase_ms=None):
     """CustomSimpleTrainer.copy_and_paste(labeled, unlabeled) for a whole batch in one sequence of launches.  The reference pairs a batch
     with its own reverse, `copy_and_paste(copy.deepcopy(data[::-1]), data)` (an odd batch pairs its middle image with itself); here
@@ -141,7 +134,8 @@ def copy_and_paste(labeled, unlabeled, params=None, *, rate=1.0, random_num=True
     if any(t.device != dev for t in tensors):
         raise ValueError("copy_and_paste: every tensor must be on the same device")
     from . import _lib as L
-    from .ops import _stream
+    from . import _tables as T
+    from .ops import _p, _stream
 
     active = [p for p in range(P) if checked[p] is not None]
     if len(active) > 65535:
@@ -156,8 +150,8 @@ def copy_and_paste(labeled, unlabeled, params=None, *, rate=1.0, random_num=True
         choice, ratio, h_new, w_new, h_shift, w_shift = checked[p]
         (Hl, Wl, Nl), (Hu, Wu, Nu) = shapes_l[p], shapes_u[p]
         nc = int(choice.size)
-        li, lm, lb = _u8(labeled[p]["image"]), _u8(labeled[p]["masks"]), labeled[p]["boxes"].contiguous()
-        ui, um = _u8(unlabeled[p]["image"]), _u8(unlabeled[p]["masks"])
+        li, lm, lb = T.as_u8(labeled[p]["image"]), T.as_u8(labeled[p]["masks"]), labeled[p]["boxes"].contiguous()
+        ui, um = T.as_u8(unlabeled[p]["image"]), T.as_u8(unlabeled[p]["masks"])
         hold += [li, lm, lb, ui, um]
         e = tab[k]
         e.l_image, e.l_masks, e.l_boxes, e.u_image = li.data_ptr(), lm.data_ptr(), lb.data_ptr(), ui.data_ptr()
@@ -184,31 +178,18 @@ def copy_and_paste(labeled, unlabeled, params=None, *, rate=1.0, random_num=True
             out = torch.empty(out_off, dtype=torch.uint8, device=dev)
             for k in range(len(active)):
                 tab[k].out_image, tab[k].out_masks = out.data_ptr() + out_offs[k][0], out.data_ptr() + out_offs[k][1]
-            ntab = ctypes.sizeof(L.CpPair) * len(active)
-            host = np.concatenate([np.frombuffer(tab, dtype=np.uint8)[:ntab], np.concatenate(choices).view(np.uint8)])
-            buf = torch.from_numpy(host).to(dev)                 # the one host-to-device copy of the tables
+            buf, (o_choice,) = T.upload(tab, len(active), dev, [np.concatenate(choices)])  # the one host-to-device copy of the tables
+            choice_dev = buf[o_choice:]
             res = torch.zeros(row_off * 6, dtype=torch.int32, device=dev)      # stats int32 [rows][2] | boxes f32 [rows][4]
             boxes_dev = res[row_off * 2:].view(torch.float32).view(row_off, 4)
             nbytes = L.lib().umr_copy_paste_workspace(word_off, inter_off)
             ws = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=dev)
-            vp = ctypes.c_void_p
 
             def launch(phases):
-                L.check(L.lib().umr_copy_paste(vp(buf.data_ptr()), len(active), vp(buf.data_ptr() + ntab), choice_off, word_off, inter_off,
-                                               row_off, max_wpm, max_nc, max_nu, phases, vp(res.data_ptr()), vp(res.data_ptr() + row_off * 8),
-                                               vp(ws.data_ptr()), nbytes, _stream()), "umr_copy_paste")
-            if _phase_ms is None:
-                launch(7)
-            else:                                                # tools/copy_paste_bench.py: the three parts between events
-                ev = [torch.cuda.Event(enable_timing=True) for _ in range(4)]
-                for i, ph in enumerate((1, 2, 4)):
-                    ev[i].record()
-                    launch(ph)
-                ev[3].record()
+                L.check(L.lib().umr_copy_paste(_p(buf), len(active), _p(choice_dev), choice_off, word_off, inter_off, row_off, max_wpm, max_nc,
+                                               max_nu, phases, _p(res), _p(boxes_dev), _p(ws), nbytes, _stream()), "umr_copy_paste")
+            T.timed(launch, (("resize_paste", 1), ("overlap", 2), ("compose", 4)), _phase_ms)      # tools/copy_paste_bench.py times the three parts
             stats_h = res[:row_off * 2].cpu().numpy().reshape(row_off, 2)      # the call's only synchronisation
-            if _phase_ms is not None:
-                for name, i in (("resize_paste", 0), ("overlap", 1), ("compose", 2)):
-                    _phase_ms[name] = _phase_ms.get(name, 0.0) + ev[i].elapsed_time(ev[i + 1])
         # ---- what the flags say: per pair the rows to gather and the sources, uploaded as one index buffer
         plans, idx_parts, n_idx = [None] * P, [], 0
         for k, p in enumerate(active):

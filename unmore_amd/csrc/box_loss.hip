@@ -39,10 +39,10 @@ constexpr float BL_SCALE_CLAMP = (float)4.135166556742356;   // log(1000 / 16) r
 
 struct BlW { float x, y, w, h; };                     // the Box2BoxTransform weights
 
-struct BlPartial {                                    // one per workgroup, 48 bytes
-    double cls, box;
-    int32_t c[8];                                     // rows, fg, pred == gt, fg & pred == gt, fg & pred == bg, dropped, bad, (padding)
-};
+static_assert(sizeof(umr_bl_image) == 56 && offsetof(umr_bl_image, width) == 52, "umr_bl_image is mirrored by _lib.BlImage");
+
+using Partial = SumPartial<2, 7>;                     // one per workgroup, 48 bytes: the classification and the box sum; rows, fg, pred == gt,
+                                                      // fg & pred == gt, fg & pred == bg, dropped, bad
 
 __device__ __forceinline__ int bl_find(const umr_bl_image* __restrict__ images, int n_images, int chunk) {
     int lo = 0, hi = n_images;
@@ -107,41 +107,11 @@ __device__ __forceinline__ float bl_clip(float v, float hi) { return v < 0.f ? 0
 
 // the sum of v over the workgroup, in every thread; red: 4 ints of LDS
 __device__ __forceinline__ int bl_block_sum(int v, int* red) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    v = wave_sum(v);
     __syncthreads();
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
     __syncthreads();
     return red[0] + red[1] + red[2] + red[3];
-}
-
-template <typename V> __device__ __forceinline__ V bl_wave_sum(V v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// sums over the workgroup in a fixed order; valid in thread 0
-__device__ __forceinline__ void bl_block_sum2(double (&d)[2], long long (&n)[7], double* red_d, long long* red_n) {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    d[0] = bl_wave_sum(d[0]);
-    d[1] = bl_wave_sum(d[1]);
-#pragma unroll
-    for (int k = 0; k < 7; ++k) n[k] = bl_wave_sum(n[k]);
-    __syncthreads();
-    if (lane == 0) {
-        red_d[wv * 2] = d[0];
-        red_d[wv * 2 + 1] = d[1];
-#pragma unroll
-        for (int k = 0; k < 7; ++k) red_n[wv * 7 + k] = n[k];
-    }
-    __syncthreads();
-    if (tid == 0) {
-        d[0] = ((red_d[0] + red_d[2]) + red_d[4]) + red_d[6];
-        d[1] = ((red_d[1] + red_d[3]) + red_d[5]) + red_d[7];
-#pragma unroll
-        for (int k = 0; k < 7; ++k) n[k] = red_n[k] + red_n[7 + k] + red_n[14 + k] + red_n[21 + k];
-    }
 }
 
 // ---------------------------------------------------------------------------------------------------------------- match and label
@@ -315,7 +285,7 @@ __global__ __launch_bounds__(BL_THREADS) void bl_loss_kernel(const umr_bl_image*
                                                              BlW bw, float beta, int soft, int drop_mode, float iou_thresh,
                                                              const float* __restrict__ weights_in, const float* __restrict__ single,
                                                              float* __restrict__ weights_out, T* __restrict__ grad_scores,
-                                                             T* __restrict__ grad_deltas, BlPartial* __restrict__ partials) {
+                                                             T* __restrict__ grad_deltas, Partial* __restrict__ partials) {
     __shared__ float set[BL_UNIQUE_ROWS][5];                               // the image's first rows of matched gt_boxes, with their areas
     __shared__ int red[4];
     __shared__ double red_d[8];
@@ -324,7 +294,7 @@ __global__ __launch_bounds__(BL_THREADS) void bl_loss_kernel(const umr_bl_image*
     const umr_bl_image im = images[bl_find(images, n_images, chunk)];
     const bool need_gt = LOSS || drop_mode == 2;
     if (!bl_entry_ok(im, chunk, R) || (need_gt && !im.gt_boxes) || (LOSS && !(im.gt_classes && (!soft || im.gt_scores)))) {
-        if (LOSS && tid == 0) partials[chunk] = BlPartial{0.0, 0.0, {0, 0, 0, 0, 0, 0, 0, 0}};
+        if (LOSS && tid == 0) partials[chunk] = Partial{};
         return;
     }
     // ---- the drop-loss ground-truth set: the first n_set rows, n_set = the number of DISTINCT rows among the first min(100, R_i)
@@ -463,11 +433,11 @@ __global__ __launch_bounds__(BL_THREADS) void bl_loss_kernel(const umr_bl_image*
         }
     }
     if constexpr (LOSS) {
-        bl_block_sum2(sums, n, red_d, red_n);
+        block_sum_fixed(sums, n, red_d, red_n);
         if (tid == 0) {
-            BlPartial q;
-            q.cls = sums[0];
-            q.box = sums[1];
+            Partial q;
+            q.d[0] = sums[0];
+            q.d[1] = sums[1];
 #pragma unroll
             for (int c = 0; c < 7; ++c) q.c[c] = (int32_t)n[c];
             q.c[7] = 0;
@@ -476,21 +446,14 @@ __global__ __launch_bounds__(BL_THREADS) void bl_loss_kernel(const umr_bl_image*
     }
 }
 
-__global__ __launch_bounds__(BL_THREADS) void bl_finish_kernel(const BlPartial* __restrict__ partials, int n_partials, double rows,
+__global__ __launch_bounds__(BL_THREADS) void bl_finish_kernel(const Partial* __restrict__ partials, int n_partials, double rows,
                                                                float* __restrict__ loss_cls, float* __restrict__ loss_box,
                                                                int64_t* __restrict__ counters) {
     __shared__ double red_d[8];
     __shared__ long long red_n[28];
-    double d[2] = {0.0, 0.0};
-    long long n[7] = {0, 0, 0, 0, 0, 0, 0};
-    for (int i = threadIdx.x; i < n_partials; i += BL_THREADS) {
-        const BlPartial q = partials[i];
-        d[0] += q.cls;
-        d[1] += q.box;
-#pragma unroll
-        for (int k = 0; k < 7; ++k) n[k] += q.c[k];
-    }
-    bl_block_sum2(d, n, red_d, red_n);
+    double d[2];
+    long long n[7];
+    partials_sum_fixed(partials, n_partials, d, n, red_d, red_n);
     if (threadIdx.x == 0) {
         loss_cls[0] = rows > 0 ? (float)(d[0] / rows) : 0.f;               // the mean over R
         loss_box[0] = (float)(d[1] / (rows > 1.0 ? rows : 1.0));            // / max(R, 1)
@@ -519,7 +482,7 @@ int bl_check_weights(float wx, float wy, float ww, float wh, BlW* out) {
 
 extern "C" int64_t umr_box_loss_workspace(int64_t n_chunks) {
     if (n_chunks < 0 || n_chunks > INT_MAX) return -1;
-    return std::max<int64_t>(n_chunks, 1) * (int64_t)sizeof(BlPartial);
+    return std::max<int64_t>(n_chunks, 1) * (int64_t)sizeof(Partial);
 }
 
 extern "C" int64_t umr_box_decode_workspace(int64_t R, int64_t n_chunks) {
@@ -640,7 +603,7 @@ extern "C" int umr_box_loss(const umr_bl_image* images, int n_images, int64_t R,
     UMR_CHECK_ARG(workspace_bytes >= umr_box_loss_workspace(n_chunks), "box_loss: workspace too small");
     UMR_CHECK_ARG(R == 0 || (scores && deltas && weights && grad_scores && grad_deltas), "box_loss: null scores, deltas, weights or gradient");
     hipStream_t s = (hipStream_t)stream;
-    BlPartial* partials = (BlPartial*)workspace;
+    Partial* partials = (Partial*)workspace;
     if ((phases & 1) && R > 0) {
         if (dtype == UMR_F32)
             bl_loss_kernel<float, true><<<(int)n_chunks, BL_THREADS, 0, s>>>(images, n_images, (int)R, K1, (long long)num_classes,

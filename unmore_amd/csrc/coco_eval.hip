@@ -195,9 +195,7 @@ __global__ __launch_bounds__(CE_THREADS) void mask_iou_kernel(const int64_t* __r
             int mine = 0;
 #pragma unroll
             for (int i = 0; i < MI_TD; ++i) {
-                int v = acc[jj][i];
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+                const int v = wave_sum(acc[jj][i]);
                 if (lane == i) mine = v;
             }
             if (j < cg && lane < cd) {

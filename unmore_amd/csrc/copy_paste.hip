@@ -40,6 +40,8 @@ struct CpTotals {                                    // the extents of the share
     int64_t choice, words, inter, rows;
 };
 
+static_assert(sizeof(umr_cp_pair) == 152 && offsetof(umr_cp_pair, reserved) == 148, "umr_cp_pair is mirrored by _lib.CpPair");
+
 struct CpPair {
     umr_cp_pair e;
     int WW;                                          // words per row
@@ -168,15 +170,11 @@ __global__ __launch_bounds__(CP_THREADS) void cp_overlap_kernel(const umr_cp_pai
 #pragma unroll
         for (int jj = 0; jj < OV_TE / 4; ++jj) {
             const int j = wv + jj * 4;
-            int a = ar[jj];
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+            const int a = wave_sum(ar[jj]);
             if (lane == 0 && j < cj && i0 == 0) I[(int64_t)e.nc * e.Nu + j0 + j] = a;
 #pragma unroll
             for (int i = 0; i < OV_TP; ++i) {
-                int v = acc[jj][i];
-#pragma unroll
-                for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+                const int v = wave_sum(acc[jj][i]);
                 if (lane == 0 && j < cj && i < ci) I[(int64_t)(i0 + i) * e.Nu + j0 + j] = v;
             }
         }

@@ -257,6 +257,7 @@ __device__ __forceinline__ void block_scan_min_w(int* a, int* part, int lo, int 
 // twenty 500x375 masks (rocprofv3 kernel trace); dt3x3_kernel itself is left as it is.
 // The maximum is taken over the FLOAT32 field: (float)fixed is monotone in fixed and the 2^-16 scale is exact, so the order is
 // that of (float)fixed; equal floats keep the lowest raster index, as numpy's argmax does.
+static_assert(sizeof(umr_ragged_src) == 24 && offsetof(umr_ragged_src, W) == 20, "umr_ragged_src is mirrored by _lib.RaggedSrc");
 __global__ __launch_bounds__(LT) void bg_square_kernel(const umr_ragged_src* __restrict__ items, int* __restrict__ ws, int64_t slab,
                                                        int32_t* __restrict__ boxes) {
     __shared__ int prev[MAXW + 2];   // previous row; prev[0] and prev[W + 1] are the zero border and are never overwritten

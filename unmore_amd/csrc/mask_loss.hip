@@ -51,10 +51,10 @@ constexpr float ML_MAX_COORD = 1048576.f;            // 2^20
 constexpr int64_t ML_MAX_LDS = 160 * 1024;
 constexpr long long ML_SPLIT_SAMPLES = 65536;        // a proposal with more samples than this is shared by the workgroups of its grid row
 
-struct MlPartial {                                   // one per proposal, 32 bytes
-    double loss;
-    int32_t c[6];                                    // incorrect, positive, false positive, false negative, bad, (padding)
-};
+static_assert(sizeof(umr_ml_image) == 48 && offsetof(umr_ml_image, index64) == 44, "umr_ml_image is mirrored by _lib.MlImage");
+
+using Partial = SumPartial<1, 5>;                    // one per workgroup, 32 bytes: the weighted loss; incorrect, positive, false positive,
+                                                     // false negative, bad
 
 __host__ __device__ inline int ml_cap(int size, int M) { return 2 * (size + 4) + M; }
 inline int ml_slices(int M) { return (M * M + ML_THREADS - 1) / ML_THREADS; }      // workgroups per proposal: one pass of bins each when all are used
@@ -87,38 +87,12 @@ __device__ __forceinline__ int2 ml_entry(float c, int size) {
     return make_int2(low, __float_as_int(c - (float)low));
 }
 
-template <typename V> __device__ __forceinline__ V ml_wave_sum(V v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// sums over the workgroup in a fixed order; the result is valid in thread 0
-__device__ __forceinline__ void ml_block_sum(double& d, long long (&n)[5], double* red_d, long long* red_n) {
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    d = ml_wave_sum(d);
-#pragma unroll
-    for (int k = 0; k < 5; ++k) n[k] = ml_wave_sum(n[k]);
-    __syncthreads();
-    if (lane == 0) {
-        red_d[wv] = d;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) red_n[wv * 5 + k] = n[k];
-    }
-    __syncthreads();
-    if (tid == 0) {
-        d = ((red_d[0] + red_d[1]) + red_d[2]) + red_d[3];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) n[k] = red_n[k] + red_n[5 + k] + red_n[10 + k] + red_n[15 + k];
-    }
-}
-
 template <typename T, bool LOSS>
 __global__ __launch_bounds__(ML_THREADS) void ml_main_kernel(const umr_ml_image* __restrict__ images, int n_images, int R, int C, int M,
                                                              int max_h, int max_w, const T* __restrict__ logits,
                                                              const int64_t* __restrict__ classes, const float* __restrict__ weights,
                                                              float inv_n, uint8_t* __restrict__ targets, T* __restrict__ grad,
-                                                             MlPartial* __restrict__ partials) {
+                                                             Partial* __restrict__ partials) {
     extern __shared__ __attribute__((aligned(16))) unsigned char ml_smem[];
     double* red_d = (double*)ml_smem;                                  // [4]
     long long* red_n = (long long*)(ml_smem + 32);                     // [4][5]
@@ -169,9 +143,9 @@ __global__ __launch_bounds__(ML_THREADS) void ml_main_kernel(const umr_ml_image*
     const int slices = est > ML_SPLIT_SAMPLES ? (int)gridDim.y : 1;
     const int rows_per = (M + slices - 1) / slices;
     const int ph0 = min((int)blockIdx.y * rows_per, M), ph1 = (int)blockIdx.y < slices ? min(ph0 + rows_per, M) : ph0;
-    MlPartial* partial = LOSS ? partials + ((int64_t)r * gridDim.y + blockIdx.y) : nullptr;
+    Partial* partial = LOSS ? partials + ((int64_t)r * gridDim.y + blockIdx.y) : nullptr;
     if (ph0 >= ph1) {                                                   // workgroup-uniform: nothing of this proposal is left for this workgroup
-        if (LOSS && tid == 0) *partial = MlPartial{0.0, {0, 0, 0, 0, 0, 0}};
+        if (LOSS && tid == 0) *partial = Partial{};
         return;
     }
 
@@ -215,7 +189,7 @@ __global__ __launch_bounds__(ML_THREADS) void ml_main_kernel(const umr_ml_image*
     // ---- bins
     const uint8_t* m = sampled ? im.masks + (int64_t)g * H * W : nullptr;
     const float w = (LOSS && weights) ? weights[r] : 1.f;
-    double lsum = 0.0;
+    double lsum[1] = {0.0};
     long long n[5] = {0, 0, 0, 0, 0};
     for (int bin = ph0 * M + tid; bin < ph1 * M; bin += ML_THREADS) {
         const int ph = bin / M, pw = bin - ph * M;
@@ -247,7 +221,7 @@ __global__ __launch_bounds__(ML_THREADS) void ml_main_kernel(const umr_ml_image*
                 const float x = to_f32<T>(logits[((int64_t)r * C + ch) * MM + bin]);
                 const float e = expf(-fabsf(x));
                 const float bce = (t ? 0.f : x) + fmaxf(-x, 0.f) + log1pf(e);
-                lsum += (double)(w * bce);
+                lsum[0] += (double)(w * bce);
                 const bool wrong = (x > 0.f) != t;
                 n[0] += wrong; n[1] += t; n[2] += wrong && !t; n[3] += wrong && t;
                 const float pp = 1.f / (1.f + e), qq = e * pp;          // sigmoid(|x|), sigmoid(-|x|)
@@ -258,10 +232,10 @@ __global__ __launch_bounds__(ML_THREADS) void ml_main_kernel(const umr_ml_image*
         }
     }
     if constexpr (LOSS) {
-        ml_block_sum(lsum, n, red_d, red_n);
+        block_sum_fixed(lsum, n, red_d, red_n);
         if (tid == 0) {
-            MlPartial q;
-            q.loss = lsum;
+            Partial q;
+            q.d[0] = lsum[0];
             q.c[0] = (int32_t)n[0]; q.c[1] = (int32_t)n[1]; q.c[2] = (int32_t)n[2]; q.c[3] = (int32_t)n[3];
             q.c[4] = (blockIdx.y == 0 && !(ok && class_ok)) ? 1 : 0;
             q.c[5] = 0;
@@ -270,21 +244,15 @@ __global__ __launch_bounds__(ML_THREADS) void ml_main_kernel(const umr_ml_image*
     }
 }
 
-__global__ __launch_bounds__(ML_THREADS) void ml_finish_kernel(const MlPartial* __restrict__ partials, int64_t n_partials, double n_elements,
+__global__ __launch_bounds__(ML_THREADS) void ml_finish_kernel(const Partial* __restrict__ partials, int64_t n_partials, double n_elements,
                                                                float* __restrict__ loss, int64_t* __restrict__ counts) {
     __shared__ double red_d[4];
     __shared__ long long red_n[20];
-    double d = 0.0;
-    long long n[5] = {0, 0, 0, 0, 0};
-    for (int64_t i = threadIdx.x; i < n_partials; i += ML_THREADS) {
-        const MlPartial q = partials[i];
-        d += q.loss;
-#pragma unroll
-        for (int k = 0; k < 5; ++k) n[k] += q.c[k];
-    }
-    ml_block_sum(d, n, red_d, red_n);
+    double d[1];
+    long long n[5];
+    partials_sum_fixed(partials, n_partials, d, n, red_d, red_n);
     if (threadIdx.x == 0) {
-        loss[0] = n_partials > 0 ? (float)(d / n_elements) : 0.f;
+        loss[0] = n_partials > 0 ? (float)(d[0] / n_elements) : 0.f;
 #pragma unroll
         for (int k = 0; k < 5; ++k) counts[k] = n[k];
     }
@@ -304,7 +272,7 @@ int ml_check_common(const umr_ml_image* images, int n_images, int64_t R, int M, 
 
 template <typename T, bool LOSS> void ml_launch(const umr_ml_image* images, int n_images, int R, int C, int M, int max_h, int max_w,
                                                 const void* logits, const int64_t* classes, const float* weights, float inv_n,
-                                                uint8_t* targets, void* grad, MlPartial* partials, hipStream_t s) {
+                                                uint8_t* targets, void* grad, Partial* partials, hipStream_t s) {
     const int lds = (int)ml_lds_bytes(M, max_h, max_w);
     UMR_SET_MAX_LDS_ONCE((ml_main_kernel<T, LOSS>), (int)ML_MAX_LDS);
     ml_main_kernel<T, LOSS><<<dim3(R, ml_slices(M)), ML_THREADS, lds, s>>>(images, n_images, R, C, M, max_h, max_w, (const T*)logits, classes, weights, inv_n,
@@ -315,7 +283,7 @@ template <typename T, bool LOSS> void ml_launch(const umr_ml_image* images, int 
 
 extern "C" int64_t umr_mask_loss_workspace(int64_t R, int M) {
     if (R < 0 || M < 1 || M > ML_MAX_SIDE) return -1;
-    return std::max<int64_t>(R, 1) * ml_slices(M) * (int64_t)sizeof(MlPartial);
+    return std::max<int64_t>(R, 1) * ml_slices(M) * (int64_t)sizeof(Partial);
 }
 
 extern "C" int umr_mask_targets(const umr_ml_image* images, int n_images, int64_t R, int M, int max_h, int max_w, uint8_t* targets,
@@ -342,7 +310,7 @@ extern "C" int umr_mask_loss(const umr_ml_image* images, int n_images, int64_t R
     UMR_CHECK_ARG(R == 0 || (logits && grad), "mask_loss: null logits or gradient");
     UMR_CHECK_ARG(R == 0 || C == 1 || gt_classes, "mask_loss: more than one channel needs gt_classes");
     hipStream_t s = (hipStream_t)stream;
-    MlPartial* partials = (MlPartial*)workspace;
+    Partial* partials = (Partial*)workspace;
     const double n_elements = (double)R * M * M;
     if ((phases & 1) && R > 0) {
         const float inv_n = (float)(1.0 / n_elements);

@@ -84,7 +84,7 @@ template <typename T> __device__ __forceinline__ float dgelu_sel(float x) {
     }
 }
 
-__device__ __forceinline__ float wave_sum(float v) {
+template <typename V> __device__ __forceinline__ V wave_sum(V v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
     return v;
@@ -93,6 +93,57 @@ __device__ __forceinline__ float wave_max(float v) {
 #pragma unroll
     for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
     return v;
+}
+
+// The loss kernels' sums over a workgroup of 256 threads, in a fixed order: the butterfly in every wave, lane 0 leaves its wave's sums
+// in LDS (red_d[wave * ND + k], red_n[wave * NN + k]) and thread 0 adds the four waves as ((w0 + w1) + w2) + w3.  Valid in thread 0.
+template <int ND, int NN>
+__device__ __forceinline__ void block_sum_fixed(double (&d)[ND], long long (&n)[NN], double* red_d, long long* red_n) {
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+#pragma unroll
+    for (int k = 0; k < ND; ++k) d[k] = wave_sum(d[k]);
+#pragma unroll
+    for (int k = 0; k < NN; ++k) n[k] = wave_sum(n[k]);
+    __syncthreads();
+    if (lane == 0) {
+#pragma unroll
+        for (int k = 0; k < ND; ++k) red_d[wv * ND + k] = d[k];
+#pragma unroll
+        for (int k = 0; k < NN; ++k) red_n[wv * NN + k] = n[k];
+    }
+    __syncthreads();
+    if (tid == 0) {
+#pragma unroll
+        for (int k = 0; k < ND; ++k) d[k] = ((red_d[k] + red_d[ND + k]) + red_d[2 * ND + k]) + red_d[3 * ND + k];
+#pragma unroll
+        for (int k = 0; k < NN; ++k) n[k] = red_n[k] + red_n[NN + k] + red_n[2 * NN + k] + red_n[3 * NN + k];
+    }
+}
+
+// what one workgroup leaves for the finishing launch: ND sums and NN counts, the counts padded to an even number
+template <int ND, int NN> struct SumPartial {
+    double d[ND];
+    int32_t c[NN + (NN & 1)];
+};
+static_assert(sizeof(SumPartial<1, 5>) == 32 && sizeof(SumPartial<2, 7>) == 48, "the loss workspaces are sized by these records");
+
+// the first half of a finishing kernel (one workgroup of 256 threads): thread t adds the partials t, t + 256, ... in index order, then
+// block_sum_fixed.  The index type is the caller's.
+template <int ND, int NN, typename I>
+__device__ __forceinline__ void partials_sum_fixed(const SumPartial<ND, NN>* __restrict__ partials, I n_partials, double (&d)[ND],
+                                                   long long (&n)[NN], double* red_d, long long* red_n) {
+#pragma unroll
+    for (int k = 0; k < ND; ++k) d[k] = 0.0;
+#pragma unroll
+    for (int k = 0; k < NN; ++k) n[k] = 0;
+    for (I i = threadIdx.x; i < n_partials; i += 256) {
+        const SumPartial<ND, NN> q = partials[i];
+#pragma unroll
+        for (int k = 0; k < ND; ++k) d[k] += q.d[k];
+#pragma unroll
+        for (int k = 0; k < NN; ++k) n[k] += q.c[k];
+    }
+    block_sum_fixed(d, n, red_d, red_n);
 }
 
 // zero page: source address for masked LDS-DMA lanes (one copy per translation unit;

@@ -166,12 +166,11 @@ def synthesize_training_items(images, masks, image_size, scale=(0.08, 1.0), use_
 # ---------------------------------------------------------------------------------------------------------------------
 # The existence classifier's training item (datasets.py:285-349, ImageNet_votecut_labeled_classifier_Dataset.__getitem__)
 # ---------------------------------------------------------------------------------------------------------------------
-import ctypes
 import random
 
 import numpy as np
 
-_RAGGED_INTS = ctypes.sizeof(L.RaggedSrc) // 4     # a table entry in int32 units (two pointers, H, W)
+from ._tables import upload
 
 
 def _ragged_upload(f32s, u8s, shapes, extra, dev):
@@ -183,9 +182,8 @@ def _ragged_upload(f32s, u8s, shapes, extra, dev):
         tab[k].f32 = f32s[k].data_ptr() if f32s[k] is not None else None
         tab[k].u8 = u8s[k].data_ptr() if u8s[k] is not None else None
         tab[k].H, tab[k].W = h, w
-    parts = [np.frombuffer(tab, dtype=np.int32)] + [np.asarray(e, dtype=np.int32).reshape(-1) for e in extra]
-    offs = np.cumsum([0] + [p.size for p in parts])[1:-1].tolist()
-    return torch.from_numpy(np.concatenate(parts)).to(dev), offs
+    buf, offs = upload(tab, n, dev, [np.asarray(e, dtype=np.int32) for e in extra])
+    return buf.view(torch.int32), [o // 4 for o in offs]
 
 
 def background_squares(full_masks):

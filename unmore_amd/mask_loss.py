@@ -6,10 +6,11 @@ weighted by the pseudo-label's score.  `mask_targets` makes the targets alone; `
 loss, the logged counters and the gradient in one sequence of launches (csrc/mask_loss.hip).  The masks are read in place through
 `mask_index`: the reference's gather of one full frame per proposal (`gt_masks[matched_idxs]`) is never made.  No CPU fallback:
 tests/mask_loss_common.py restates the method in NumPy and torch CPU ops."""
-import ctypes
-
-import numpy as np
 import torch
+
+from . import _lib as L
+from . import _tables as T
+from .ops import _p, _stream
 
 MAX_SIDE = 512
 MAX_LDS_BYTES = 160 * 1024
@@ -20,22 +21,14 @@ def _lds_bytes(side, max_h, max_w):
     return 16 * (max_h + max_w) + 32 * side + 328        # csrc/mask_loss.hip: ml_lds_bytes
 
 
-def _tensor(v):
-    return getattr(v, "tensor", v)                       # Detectron2's BitMasks / Boxes, or the tensor itself
-
-
 def _fields(item, k):
     """(masks, boxes, mask_index, gt_classes) of one image: a dict or an object with Detectron2's Instances fields"""
-    if isinstance(item, dict):
-        get = item.get
-    else:
-        def get(name):
-            return getattr(item, name, None)
+    get = T.getter(item)
     masks, boxes = get("gt_masks"), get("proposal_boxes")
     if masks is None or boxes is None:
         raise ValueError(f"mask_loss: instances[{k}] needs gt_masks and proposal_boxes")
     index, classes = get("mask_index"), get("gt_classes")
-    return _tensor(masks), _tensor(boxes), index, classes
+    return T.unwrap(masks), T.unwrap(boxes), index, classes
 
 
 def _check_image(masks, boxes, index, what):
@@ -71,29 +64,15 @@ def _check_side(side, images):
 
 
 def _device(tensors, what):
-    """the one device of `tensors`: ValueError when they differ, RuntimeError when it is not the GPU"""
-    devs = {t.device for t in tensors}
-    if len(devs) > 1:
-        raise ValueError(f"mask_loss: every tensor must be on the same device, got {sorted(str(d) for d in devs)}")
-    dev = devs.pop()
-    if dev.type != "cuda":
-        raise RuntimeError(f"unmore_amd.mask_loss.{what} runs on the MI355X only (no CPU fallback); "
-                           "tests/mask_loss_common.py restates it on the host (mask_targets_np, loss_reference)")
-    return dev
-
-
-def _u8(t):
-    t = t.contiguous()
-    return t.view(torch.uint8) if t.dtype == torch.bool else t
+    return T.one_device(tensors, "mask_loss", what, " (mask_targets_np, loss_reference)")
 
 
 def _upload_table(images, dev):
     """one umr_ml_image per image, in one host-to-device copy: (device buffer, what the table points into, R)"""
-    from . import _lib as L
     tab = (L.MlImage * max(len(images), 1))()
     hold, first = [], 0
     for k, (masks, boxes, index) in enumerate(images):
-        m, b = _u8(masks), boxes.contiguous()
+        m, b = T.as_u8(masks), boxes.contiguous()
         i = None if index is None else index.contiguous()
         hold += [m, b, i]
         e = tab[k]
@@ -101,8 +80,7 @@ def _upload_table(images, dev):
         e.H, e.W, e.G, e.first, e.R = int(m.shape[1]), int(m.shape[2]), int(m.shape[0]), first, int(b.shape[0])
         e.index64 = int(i is not None and i.dtype == torch.int64)
         first += int(b.shape[0])
-    host = np.frombuffer(tab, dtype=np.uint8)[:ctypes.sizeof(L.MlImage) * len(images)].copy()
-    return torch.from_numpy(host).to(dev), hold, first
+    return T.upload(tab, len(images), dev)[0], hold, first
 
 
 def mask_targets(masks, boxes, mask_index=None, side=28):
@@ -126,23 +104,17 @@ def mask_targets(masks, boxes, mask_index=None, side=28):
     if not images:
         raise ValueError("mask_targets: no image")
     dev = _device([t for im in images for t in im if t is not None], "mask_targets")
-    from . import _lib as L
-    from .ops import _stream
     with torch.cuda.device(dev):
         buf, hold, R = _upload_table(images, dev)
         out = torch.empty((R, side, side), dtype=torch.uint8, device=dev)
         if R:
-            vp = ctypes.c_void_p
-            L.check(L.lib().umr_mask_targets(vp(buf.data_ptr()), len(images), R, side, max_h, max_w, vp(out.data_ptr()), _stream()),
-                    "umr_mask_targets")
+            L.check(L.lib().umr_mask_targets(_p(buf), len(images), R, side, max_h, max_w, _p(out), _stream()), "umr_mask_targets")
     del hold
     return out.view(torch.bool)
 
 
 def _run(logits, images, classes, weights, side, max_h, max_w, dev, want_targets, _phase_ms=None):
     """the launches: (loss f32 0-dim, grad like logits, counters int64 [5], targets bool or None)"""
-    from . import _lib as L
-    from .ops import _stream
     R, C = int(logits.shape[0]), int(logits.shape[1])
     with torch.cuda.device(dev):
         loss, counters = torch.zeros((), dtype=torch.float32, device=dev), torch.zeros(5, dtype=torch.int64, device=dev)
@@ -153,26 +125,12 @@ def _run(logits, images, classes, weights, side, max_h, max_w, dev, want_targets
         buf, hold, _ = _upload_table(images, dev)
         nbytes = L.lib().umr_mask_loss_workspace(R, side)
         ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
-        vp = ctypes.c_void_p
 
         def launch(phases):
-            L.check(L.lib().umr_mask_loss(vp(buf.data_ptr()), len(images), R, C, side, max_h, max_w, vp(logits.data_ptr()),
-                                          L.BF16 if logits.dtype == torch.bfloat16 else L.F32,
-                                          None if classes is None else vp(classes.data_ptr()),
-                                          None if weights is None else vp(weights.data_ptr()), phases,
-                                          None if targets is None else vp(targets.data_ptr()), vp(grad.data_ptr()),
-                                          vp(loss.data_ptr()), vp(counters.data_ptr()), vp(ws.data_ptr()), nbytes, _stream()), "umr_mask_loss")
-        if _phase_ms is None:
-            launch(3)
-        else:                                                                  # tools/mask_loss_bench.py: the two parts between events
-            ev = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
-            for i, ph in enumerate((1, 2)):
-                ev[i].record()
-                launch(ph)
-            ev[2].record()
-            ev[2].synchronize()
-            for name, i in (("targets_loss", 0), ("finish", 1)):
-                _phase_ms[name] = _phase_ms.get(name, 0.0) + ev[i].elapsed_time(ev[i + 1])
+            L.check(L.lib().umr_mask_loss(_p(buf), len(images), R, C, side, max_h, max_w, _p(logits), T.dtype_code(logits), _p(classes),
+                                          _p(weights), phases, _p(targets), _p(grad), _p(loss), _p(counters), _p(ws), nbytes, _stream()),
+                    "umr_mask_loss")
+        T.timed(launch, (("targets_loss", 1), ("finish", 2)), _phase_ms)     # tools/mask_loss_bench.py times the two parts
         del hold
     return loss, grad, counters, (None if targets is None else targets.view(torch.bool))
 
