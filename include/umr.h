@@ -769,6 +769,48 @@ int umr_box_loss(const umr_bl_image* images, int n_images, int64_t R, int64_t n_
                  void* grad_scores, void* grad_deltas, float* loss_cls, float* loss_box_reg, int64_t* counters, void* workspace,
                  int64_t workspace_bytes, umr_stream_t stream);
 
+/* ---- the detector's inference tail (cad/modeling/roi_heads/fast_rcnn.py:52-179, roi_heads.py:1048-1091, meta_arch/rcnn.py:242-256 with
+ * Detectron2's detector_postprocess, cad/evaluation/coco_evaluation.py:398-457; csrc/det_post.hip) ----------------------------------------
+ * det_select (fast_rcnn_inference for a batch): per image scores [R,K+1] (background last) and boxes [R,4] (box_classes == 1) or [R,K*4]
+ *   (box_classes == K), float32.  A row with a non-finite box or score entry is dropped; boxes are clipped to (height, width); the
+ *   candidates are the pairs p = r * K + c with score[r,c] > score_thresh, in p order; they are ranked by descending score, equal scores
+ *   in p order; greedy NMS per class: a candidate is suppressed iff an earlier kept one of its class has
+ *   inter / ((area_a + area_b) - inter) > nms_thresh (float32, every operation rounded on its own; NaN suppresses nothing); the first
+ *   topk kept ones (all when topk < 0) of image k go, in rank order, to the rows [out_first, out_first + counts[k]) of out_boxes [total_out,4],
+ *   out_scores, out_classes and out_rows (the input row).  Table: cand_first = the sum of R * K before the image, total_cand their
+ *   total, max_cand their maximum (<= 8192); cap = the image's output slots (R * K, or min(R * K, topk)), out_first / total_out their
+ *   prefix sums; mat_first = the sum of R * K * ceil(R * K / 64) before the image (64-bit words of its suppression matrix), total_words
+ *   their total.  workspace >= det_select_workspace(n_images, total_cand, total_words) bytes, 16-byte aligned.  phases: 1 = candidates
+ *   and ranks, 2 = the suppression matrix, 4 = the scan; 7 = all (three launches).  Nothing is read back; no atomics.
+ * det_scale: rec [n,8] = the box scaled by rowinfo's (sx, sy) and clipped to its (H, W) as x0, y0, x1, y1, then x1 - x0, y1 - y0,
+ *   1 / 0 for width > 0 and height > 0, and 0.  rowinfo [n,4] 32-bit words: float sx, float sy, int32 H, int32 W.
+ * det_paste (paste_masks_in_image): logits [N,C,M,M] UMR_F32 / UMR_BF16, channel classes[k] when C > 1 (NULL allowed for C == 1);
+ *   sigmoid, then F.grid_sample(align_corners=False, zero padding) into box k (boxes + k * box_stride floats), set iff the sample
+ *   >= threshold (in [0.5, 1]); out u8 [N,H,W], ZEROED BY THE CALLER.  The float32 operation order is written out in csrc/det_post.hip.  M <= 128.
+ * det_paste_rle: the COCO run-length strings of those masks without writing them, mask k in its own frame (frames + k * frame_stride:
+ *   int32 H, W); the measure pass / write pass protocol of umr_rle_encode. */
+typedef struct umr_dp_image {
+    const float* boxes;          /* [R,4] or [R,K*4] */
+    const float* scores;         /* [R,K+1] */
+    int64_t mat_first;
+    int32_t R;
+    int32_t cand_first;
+    int32_t out_first;
+    int32_t cap;
+    float height, width;         /* the frame, for the clip */
+} umr_dp_image;
+int64_t umr_det_select_workspace(int n_images, int64_t total_cand, int64_t total_words);
+int umr_det_select(const umr_dp_image* images, int n_images, int K, int box_classes, int64_t total_cand, int max_cand, int64_t total_words,
+                   int64_t total_out, float score_thresh, float nms_thresh, int topk, int phases, float* out_boxes, float* out_scores,
+                   int64_t* out_classes, int64_t* out_rows, int32_t* counts, void* workspace, int64_t workspace_bytes,
+                   umr_stream_t stream);
+int umr_det_scale(const float* boxes, const void* rowinfo, int64_t n, float* rec, umr_stream_t stream);
+int umr_det_paste(const void* logits, int dtype, int64_t N, int C, int M, const int64_t* classes, const float* boxes, int box_stride, int H,
+                  int W, float threshold, uint8_t* out, umr_stream_t stream);
+int umr_det_paste_rle(const void* logits, int dtype, int64_t N, int C, int M, const int64_t* classes, const float* boxes, int box_stride,
+                      const int32_t* frames, int frame_stride, float threshold, int64_t* sizes, const int64_t* offsets, uint8_t* chars,
+                      int64_t chars_capacity, umr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -72,6 +72,11 @@ class BlImage(ctypes.Structure):   # umr_bl_image
                 ("chunk_first", _i32), ("height", ctypes.c_float), ("width", ctypes.c_float)]
 
 
+class DpImage(ctypes.Structure):   # umr_dp_image
+    _fields_ = [("boxes", _vp), ("scores", _vp), ("mat_first", _i64), ("R", _i32), ("cand_first", _i32), ("out_first", _i32), ("cap", _i32),
+                ("height", ctypes.c_float), ("width", ctypes.c_float)]
+
+
 class PermEntry(ctypes.Structure):   # umr_perm_entry
     _fields_ = [("src", _vp), ("dst", _vp), ("d", _i32 * 4), ("sstride", _i64 * 4), ("soff", _i64), ("dtype_in", _i32), ("dtype_out", _i32),
                 ("blk_start", _i64), ("e", _i32 * 4), ("ord", _i32 * 4), ("rowlen", _i64)]
@@ -182,6 +187,11 @@ _SIGS = {
     "umr_box_drop_weights": [_vp, _i32, _i64, _i64, _vp, _i32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp],
     "umr_box_loss": [_vp, _i32, _i64, _i64, _i32, _i64, _vp, _vp, _i32, _f32, _f32, _f32, _f32, _f32, _i32, _i32, _f32, _vp, _vp, _i32, _vp, _vp,
                      _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+    "umr_det_select_workspace": [_i32, _i64, _i64],
+    "umr_det_select": [_vp, _i32, _i32, _i32, _i64, _i32, _i64, _i64, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
+    "umr_det_scale": [_vp, _vp, _i64, _vp, _vp],
+    "umr_det_paste": [_vp, _i32, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp],
+    "umr_det_paste_rle": [_vp, _i32, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _f32, _vp, _vp, _vp, _i64, _vp],
     "umr_mask_components": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
     "umr_nms_workspace": [_i32],
     "umr_nms": [_vp, _vp, _i32, _f32, _vp, _i64, _vp, _vp, _vp],
@@ -234,7 +244,7 @@ def lib():
                    "umr_distance_transform_workspace", "umr_gemm_nt_workspace", "umr_gemm_nt_x3_workspace", "umr_nms_workspace",
                    "umr_bn_train_workspace", "umr_bg_square_workspace", "umr_rle_decode_workspace", "umr_mask_iou_workspace",
                    "umr_poly_rle_workspace", "umr_copy_paste_workspace", "umr_mask_loss_workspace", "umr_box_loss_workspace",
-                   "umr_box_decode_workspace"):
+                   "umr_box_decode_workspace", "umr_det_select_workspace"):
             getattr(_lib, fn).restype = ctypes.c_int64
     return _lib
 
