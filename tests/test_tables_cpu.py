@@ -1,5 +1,5 @@
 """unmore_amd._tables without a GPU: the layouts of the ctypes mirrors of the device tables (the csrc files assert the same numbers on the C
-structs), the upload of a table with its extras, the one-device check and the untimed path of `timed`."""
+structs), the upload of a table with its extras, the workspace buffer, the one-device check and the untimed path of `timed`."""
 import ctypes
 
 import numpy as np
@@ -11,7 +11,8 @@ from unmore_amd import _tables as T
 
 
 @pytest.mark.parametrize("mirror,size,last,offset", [(L.RaggedSrc, 24, "W", 20), (L.CpPair, 152, "reserved", 148),
-                                                     (L.MlImage, 48, "index64", 44), (L.BlImage, 56, "width", 52)])
+                                                     (L.MlImage, 48, "index64", 44), (L.BlImage, 56, "width", 52),
+                                                     (L.DpImage, 48, "width", 44)])
 def test_mirrors_keep_the_layout_the_kernels_assert(mirror, size, last, offset):
     assert ctypes.sizeof(mirror) == size
     assert mirror._fields_[-1][0] == last and getattr(mirror, last).offset == offset
@@ -43,6 +44,12 @@ def test_upload_copies_the_first_entries_then_the_extras():
 def test_upload_of_no_entries_is_an_empty_table():
     buf, offs = T.upload((L.BlImage * 1)(), 0, torch.device("cpu"))
     assert buf.dtype == torch.uint8 and buf.numel() == 0 and offs == []
+
+
+def test_workspace_rounds_up_to_16_bytes_and_is_never_empty():
+    for nbytes, size in ((0, 16), (1, 16), (16, 16), (17, 32), (-1, 16)):    # -1: what a *_workspace function returns for bad arguments
+        ws = T.workspace(nbytes, torch.device("cpu"))
+        assert ws.dtype == torch.uint8 and ws.dim() == 1 and ws.numel() == size and ws.device.type == "cpu", nbytes
 
 
 def test_one_device():

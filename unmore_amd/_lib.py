@@ -1,10 +1,14 @@
 """ctypes binding of the C-ABI library (include/umr.h).  Fails loudly when the
-HIP library is missing: there is no CPU / PyTorch fallback in the product path."""
+HIP library is missing: there is no CPU / PyTorch fallback in the product path.
+Every function's argument and return types are read from the header's prototypes when
+this module is imported; only the descriptor structs are mirrored by hand (MIRRORS)."""
 import ctypes
 import os
+import re
 import subprocess
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
+HEADER = os.path.join(_HERE, "..", "include", "umr.h")   # the file csrc/umr_common.h includes: argument and return types are read from it
 LIB_PATH = os.environ.get("UMR_LIB") or os.path.join(_HERE, "lib", "libumr.so")   # UMR_LIB: another build of the library (the fenced split-K one: libumr_fence.so)
 CSRC = os.path.join(_HERE, "csrc")
 
@@ -39,22 +43,22 @@ class GemmTnDesc(ctypes.Structure):
                 ("x_rows_in", _i32), ("x_rows_out", _i32), ("x_row_off", _i32)]
 
 
-class AdamPackEntry(ctypes.Structure):   # umr_adam_pack_entry
+class AdamPackEntry(ctypes.Structure):
     _fields_ = [("p", _vp), ("g", _vp), ("m", _vp), ("v", _vp), ("dst_lin", _vp), ("dst_t", _vp), ("n", _i64), ("N", _i32), ("K", _i32),
                 ("blk_start", _i64)]
 
 
-class BnBwdDesc(ctypes.Structure):   # umr_bn_bwd_desc
+class BnBwdDesc(ctypes.Structure):
     _fields_ = [("dy", _vp), ("dpool", _vp), ("y", _vp), ("z", _vp * 2), ("mean", _vp * 2), ("rstd", _vp * 2), ("gamma", _vp * 2),
                 ("dgamma", _vp * 2), ("dbeta", _vp * 2), ("dz", _vp * 2), ("g_out", _vp), ("workspace", _vp), ("workspace_bytes", _i64),
                 ("rows_per_batch", _i64), ("pool_scale", ctypes.c_float), ("M", _i32), ("C", _i32), ("nbranch", _i32), ("dtype", _i32)]
 
 
-class RaggedSrc(ctypes.Structure):   # umr_ragged_src
+class RaggedSrc(ctypes.Structure):
     _fields_ = [("f32", _vp), ("u8", _vp), ("H", _i32), ("W", _i32)]
 
 
-class CpPair(ctypes.Structure):   # umr_cp_pair
+class CpPair(ctypes.Structure):
     _fields_ = [("l_image", _vp), ("l_masks", _vp), ("l_boxes", _vp), ("u_image", _vp), ("u_masks", _vp), ("out_image", _vp), ("out_masks", _vp),
                 ("word_off", _i64), ("inter_off", _i64), ("row_off", _i64), ("choice_off", _i64),
                 ("Hl", _i32), ("Wl", _i32), ("Nl", _i32), ("Hu", _i32), ("Wu", _i32), ("Nu", _i32), ("nc", _i32), ("h_new", _i32), ("w_new", _i32),
@@ -62,24 +66,30 @@ class CpPair(ctypes.Structure):   # umr_cp_pair
                 ("reserved", _i32)]
 
 
-class MlImage(ctypes.Structure):   # umr_ml_image
+class MlImage(ctypes.Structure):
     _fields_ = [("masks", _vp), ("boxes", _vp), ("index", _vp), ("H", _i32), ("W", _i32), ("G", _i32), ("first", _i32), ("R", _i32),
                 ("index64", _i32)]
 
 
-class BlImage(ctypes.Structure):   # umr_bl_image
+class BlImage(ctypes.Structure):
     _fields_ = [("boxes", _vp), ("gt_boxes", _vp), ("gt_classes", _vp), ("gt_scores", _vp), ("first", _i32), ("R", _i32), ("G", _i32),
                 ("chunk_first", _i32), ("height", ctypes.c_float), ("width", ctypes.c_float)]
 
 
-class DpImage(ctypes.Structure):   # umr_dp_image
+class DpImage(ctypes.Structure):
     _fields_ = [("boxes", _vp), ("scores", _vp), ("mat_first", _i64), ("R", _i32), ("cand_first", _i32), ("out_first", _i32), ("cap", _i32),
                 ("height", ctypes.c_float), ("width", ctypes.c_float)]
 
 
-class PermEntry(ctypes.Structure):   # umr_perm_entry
+class PermEntry(ctypes.Structure):
     _fields_ = [("src", _vp), ("dst", _vp), ("d", _i32 * 4), ("sstride", _i64 * 4), ("soff", _i64), ("dtype_in", _i32), ("dtype_out", _i32),
                 ("blk_start", _i64), ("e", _i32 * 4), ("ord", _i32 * 4), ("rowlen", _i64)]
+
+
+# the header's structs and their mirrors above: tests/test_abi_cpu.py compares every size and offset with what a C compiler gives
+MIRRORS = {"umr_gemm_desc": GemmDesc, "umr_gemm_tn_desc": GemmTnDesc, "umr_adam_pack_entry": AdamPackEntry, "umr_bn_bwd_desc": BnBwdDesc,
+           "umr_ragged_src": RaggedSrc, "umr_cp_pair": CpPair, "umr_ml_image": MlImage, "umr_bl_image": BlImage, "umr_dp_image": DpImage,
+           "umr_perm_entry": PermEntry}
 
 
 def build(verbose=False, jobs=8):
@@ -97,136 +107,45 @@ def build(verbose=False, jobs=8):
 _lib = None
 _count = [0]     # launches checked so far (graphs.StagedCaptured skips graph segments that recorded nothing)
 
-_f32 = ctypes.c_float
-_SIGS = {
-    "umr_gemm_nt": [_vp, _vp],
-    "umr_gemm_nt_ws": [_vp, _vp, _i64, _vp],
-    "umr_gemm_nt_workspace": [],
-    "umr_gemm_nt_splits": [_vp, _i64],
-    "umr_gemm_nt_rowreduce_ok": [_vp],
-    "umr_label_synthesis_workspace": [_i32, _i32, _i32],
-    "umr_label_synthesis": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp],
-    "umr_label_synthesis_cropped": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp],
-    "umr_crop_resize_batch": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
-    "umr_distance_transform_workspace": [_i32, _i32, _i32],
-    "umr_distance_transform": [_vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp],
-    "umr_bg_square_workspace": [_i32, _i64],
-    "umr_bg_square": [_vp, _vp, _vp, _i64, _i32, _i32, _i64, _vp],
-    "umr_crop_resize_ragged": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
-    "umr_im2col_nchw": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
-    "umr_maxpool3x3s2": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
-    "umr_bn_fold": [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
-    "umr_bn_train_workspace": [_i32, _i32],
-    "umr_bn_train_stats": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _f32, _i32, _vp],
-    "umr_bn_train_apply": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
-    "umr_bn_train_bwd_reduce": [_vp, _vp],
-    "umr_bn_train_bwd_apply": [_vp, _vp],
-    "umr_maxpool3x3s2_bwd": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
-    "umr_stuff2_add": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
-    "umr_bce_sigmoid": [_vp, _vp, _vp, _vp, _i32, _vp],
-    "umr_head_out_finish": [_vp, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp],
-    "umr_gemm_tn": [_vp, _vp],
-    "umr_gemm_tn_workspace": [_vp],
-    "umr_layernorm_fwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _f32, _i32, _vp],
-    "umr_layernorm_bwd_workspace": [_i32, _i32],
-    "umr_layernorm_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _i64, _i32, _i32, _i32, _vp],
-    "umr_layernorm_bwd_rows": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp],
-    "umr_layernorm_bwd_params": [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _vp],
-    "umr_attention_fwd": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
-    "umr_attention_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _vp],
-    "umr_attention_bwd_workspace": [_i32, _i32, _i32],
-    "umr_patchify": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
-    "umr_bilinear_fwd": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
-    "umr_bilinear_bwd": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
-    "umr_bilinear_fwd_ex": [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
-    "umr_bilinear_bwd_ex": [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
-    "umr_pixel_shuffle": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
-    "umr_zero_stuff2": [_vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
-    "umr_permute4": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp],
-    "umr_segsum": [_vp, _vp, _i32, _i32, _i64, _i64, _i32, _i32, _i32, _i32, _vp],
-    "umr_fill_cls": [_vp, _vp, _vp, _i32, _i64, _i32, _i32, _vp],
-    "umr_cast": [_vp, _vp, _i64, _f32, _i32, _i32, _vp],
-    "umr_scale_by_device_scalar": [_vp, _vp, _vp, _i64, _vp],
-    "umr_head_out_fwd": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp],
-    "umr_head_out_bwd_workspace": [_i64, _i32],
-    "umr_head_out_bwd": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
-    "umr_loss_workspace": [],
-    "umr_objectness_loss": [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _f32, _vp],
-    "umr_adam_step": [_vp, _vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _i32, _f32, _vp],
-    "umr_adam_set_hyper": [_vp, _f32, _f32, _f32, _f32, _i32, _f32, _vp],
-    "umr_adam_step_hyper": [_vp, _vp, _vp, _vp, _i64, _vp, _vp],
-    "umr_adam_pack_step": [_vp, _i32, _i64, _vp, _vp, _vp],
-    "umr_crop_resize_bilinear": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
-    "umr_center_peaks": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
-    "umr_center_peaks_certified": [_vp, _vp, _vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _f32, ctypes.c_double, _vp],
-    "umr_boundary_deltas": [_vp, _vp, _i32, _i32, _i32, _vp],
-    "umr_mask_paste_stats": [_vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
-    "umr_mask_paste": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp],
-    "umr_rle_encode": [_vp, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp],
-    "umr_mask_paste_rle": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp],
-    "umr_rle_decode_workspace": [_i32, _i64, _i64, _i32],
-    "umr_rle_decode": [_vp, _vp, _i32, _i64, _vp, _vp, _vp, _i32, _i64, _i64, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _i64, _vp],
-    "umr_poly_rle_workspace": [_i64, _i32, _i32, _i64],
-    "umr_poly_rle": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i64, _vp],
-    "umr_mask_iou_workspace": [_i32, _i64, _i64],
-    "umr_mask_iou": [_vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
-    "umr_box_iou": [_vp, _vp, _vp, _vp, _vp, _i32, _i32, _i64, _i64, _vp, _vp],
-    "umr_coco_match": [_vp, _vp, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
-                       _vp],
-    "umr_copy_paste_workspace": [_i64, _i64],
-    "umr_copy_paste": [_vp, _i32, _vp, _i64, _i64, _i64, _i64, _i64, _i32, _i32, _i32, _vp, _vp, _vp, _i64, _vp],
-    "umr_mask_loss_workspace": [_i64, _i32],
-    "umr_mask_targets": [_vp, _i32, _i64, _i32, _i32, _i32, _vp, _vp],
-    "umr_mask_loss": [_vp, _i32, _i64, _i32, _i32, _i32, _i32, _vp, _i32, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
-    "umr_box_loss_workspace": [_i64],
-    "umr_box_decode_workspace": [_i64, _i64],
-    "umr_box_match": [_vp, _i32, _i64, _i64, _f32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "umr_box_decode": [_vp, _i32, _i64, _i64, _vp, _i32, _f32, _f32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _i64, _vp],
-    "umr_box_apply_deltas": [_vp, _i32, _vp, _i64, _f32, _f32, _f32, _f32, _vp, _vp],
-    "umr_box_get_deltas": [_vp, _vp, _i64, _f32, _f32, _f32, _f32, _vp, _vp],
-    "umr_box_drop_weights": [_vp, _i32, _i64, _i64, _vp, _i32, _f32, _f32, _f32, _f32, _f32, _vp, _vp, _vp],
-    "umr_box_loss": [_vp, _i32, _i64, _i64, _i32, _i64, _vp, _vp, _i32, _f32, _f32, _f32, _f32, _f32, _i32, _i32, _f32, _vp, _vp, _i32, _vp, _vp,
-                     _vp, _vp, _vp, _vp, _vp, _i64, _vp],
-    "umr_det_select_workspace": [_i32, _i64, _i64],
-    "umr_det_select": [_vp, _i32, _i32, _i32, _i64, _i32, _i64, _i64, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
-    "umr_det_scale": [_vp, _vp, _i64, _vp, _vp],
-    "umr_det_paste": [_vp, _i32, _i64, _i32, _i32, _vp, _vp, _i32, _i32, _i32, _f32, _vp, _vp],
-    "umr_det_paste_rle": [_vp, _i32, _i64, _i32, _i32, _vp, _vp, _i32, _vp, _i32, _f32, _vp, _vp, _vp, _i64, _vp],
-    "umr_mask_components": [_vp, _vp, _i32, _i32, _i32, _vp, _vp, _vp],
-    "umr_nms_workspace": [_i32],
-    "umr_nms": [_vp, _vp, _i32, _f32, _vp, _i64, _vp, _vp, _vp],
-    "umr_linear_head_fwd": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
-    "umr_linear_head_bwd_data": [_vp, _vp, _vp, _vp, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
-    "umr_linear_head_bwd_weight_workspace": [_i64, _i32],
-    "umr_linear_head_bwd_weight": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _vp],
-    "umr_linear_head_shift9_workspace": [_i64],
-    "umr_linear_head_shift9": [_vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _i32, _vp],
-    "umr_linear_head_gather9": [_vp, _i64, _vp, _vp, _i32, _i32, _i32, _i32, _vp],
-    "umr_small_gemm_f32": [_vp, _vp, _vp, _i32, _i32, _i32, _i64, _i64, _i64, _i64, _i64, _i64, _i32, _vp],
-    "umr_permute4_batched": [_vp, _i32, _i64, _vp, _vp],
-    "umr_split3": [_vp, _vp, _i64, _i32, _i64, _i64, _vp],
-    "umr_unsplit3": [_vp, _vp, _i64, _i32, _i64, _i64, _vp],
-    "umr_split3_rows": [_vp, _vp, _i64, _i32, _i64, _i64, _i32, _i32, _i32, _vp],
-    "umr_gemm_nt_x3_workspace": [_vp],
-    "umr_set_f32_mode": [_i32],
-    "umr_get_f32_mode": [],
-    "umr_set_cu_budget": [_i32],
-    "umr_get_cu_budget": [],
-    "umr_set_debug_option": [ctypes.c_char_p, ctypes.c_char_p],
-    "umr_get_debug_option": [ctypes.c_char_p, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)],
-    "umr_gemm_nt_ws_status": [_vp, _vp, ctypes.POINTER(ctypes.c_int)],
-    "umr_version": [],
-    "umr_last_error_string": [],
-}
+_ARG = {"int": _i32, "int32_t": _i32, "int64_t": _i64, "float": ctypes.c_float, "double": ctypes.c_double, "umr_stream_t": _vp,
+        "const char*": ctypes.c_char_p, "int*": ctypes.POINTER(ctypes.c_int)}     # every other pointer: c_void_p
+_RET = {"int": None, "int64_t": _i64, "const char*": ctypes.c_char_p}            # None: ctypes' default, a C int
 
 
-def _set_argtypes(l):
-    for name, sig in _SIGS.items():
-        getattr(l, name).argtypes = sig
+def _ctype(decl, table, proto):
+    c = re.sub(r"\s*\*\s*", "*", " ".join(decl.split()))
+    if c not in table and not (table is _ARG and c.endswith("*")):
+        raise RuntimeError(f"{HEADER}: no ctypes type for '{c}' in '{' '.join(proto.split())}'")
+    return table.get(c, _vp)
+
+
+def _read_header():
+    """The prototypes of include/umr.h as ({name: argtypes}, {name: restype, where it is not int}).  The header is the one description
+    of the boundary: a declaration this reader does not understand raises here, at import, instead of being bound by a guess."""
+    if not os.path.exists(HEADER):
+        raise RuntimeError(f"{HEADER} is missing: the ctypes binding of libumr.so is read from it")
+    text = re.sub(r"/\*.*?\*/", " ", open(HEADER).read(), flags=re.S)
+    text = re.sub(r"^[ \t]*#.*$", "", text, flags=re.M)
+    text = re.sub(r"typedef\s+struct\s+\w+\s*\{.*?\}\s*\w+\s*;", "", text, flags=re.S)
+    args, rets = {}, {}
+    for proto in text.split(";"):
+        if "(" not in proto:
+            continue                                         # enums, the stream typedef, the extern "C" braces
+        m = re.fullmatch(r"\s*(.*?)\b(umr_\w+)\s*\(([^()]*)\)\s*", proto, flags=re.S)
+        if m is None:
+            raise RuntimeError(f"{HEADER}: not a prototype this binding can read: '{' '.join(proto.split())}'")
+        ret, name, params = m.groups()
+        params = [] if params.strip() in ("", "void") else params.split(",")
+        args[name] = [_ctype(re.sub(r"\w+\s*$", "", p), _ARG, proto) for p in params]       # a parameter is its type, then its name
+        rets[name] = _ctype(ret, _RET, proto)
+    return args, {name: r for name, r in rets.items() if r is not None}
+
+
+ARGTYPES, RESTYPES = _read_header()
 
 
 def exported_symbols():
-    return sorted(_SIGS)
+    return sorted(ARGTYPES)
 
 
 def lib():
@@ -237,15 +156,11 @@ def lib():
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 "(the product has no CPU fallback)")
         _lib = ctypes.CDLL(LIB_PATH)
-        _lib.umr_last_error_string.restype = ctypes.c_char_p
-        _set_argtypes(_lib)
-        for fn in ("umr_gemm_tn_workspace", "umr_layernorm_bwd_workspace", "umr_head_out_bwd_workspace", "umr_loss_workspace",
-                   "umr_linear_head_bwd_weight_workspace", "umr_linear_head_shift9_workspace", "umr_label_synthesis_workspace", "umr_attention_bwd_workspace",
-                   "umr_distance_transform_workspace", "umr_gemm_nt_workspace", "umr_gemm_nt_x3_workspace", "umr_nms_workspace",
-                   "umr_bn_train_workspace", "umr_bg_square_workspace", "umr_rle_decode_workspace", "umr_mask_iou_workspace",
-                   "umr_poly_rle_workspace", "umr_copy_paste_workspace", "umr_mask_loss_workspace", "umr_box_loss_workspace",
-                   "umr_box_decode_workspace", "umr_det_select_workspace"):
-            getattr(_lib, fn).restype = ctypes.c_int64
+        for name, argtypes in ARGTYPES.items():
+            fn = getattr(_lib, name)
+            fn.argtypes = argtypes
+            if name in RESTYPES:
+                fn.restype = RESTYPES[name]
     return _lib
 
 

@@ -1,6 +1,7 @@
 """What the detector-side modules (mask_loss, box_loss, copy_paste, labels) share on the host: reading Detectron2-style items, the
 one-device check, the upload of a ctypes table of device pointers (_lib.RaggedSrc, CpPair, MlImage, BlImage -- the csrc files assert the
-layouts these mirror) and the bench tools' per-phase timing."""
+layouts these mirror), `workspace`, the one way from a umr_*_workspace byte count to a buffer (every module that calls such a function
+uses it), and the bench tools' per-phase timing."""
 import ctypes
 
 import numpy as np
@@ -51,6 +52,13 @@ def upload(table, n, dev, extras=()):
         offs.append(end)
         end += parts[-1].size
     return torch.from_numpy(np.concatenate(parts)).to(dev), offs
+
+
+def workspace(nbytes, dev):
+    """The buffer for what a umr_*_workspace function returned: uint8, nbytes rounded up to a multiple of 16 and never empty, so its
+    pointer is never NULL.  A negative count (the function refused its arguments) gives the 16 bytes too: the launch entry reports the
+    error.  The entry point is still passed nbytes itself."""
+    return torch.empty(max(16, (int(nbytes) + 15) // 16 * 16), dtype=torch.uint8, device=dev)
 
 
 def timed(launch, parts, _phase_ms):

@@ -235,7 +235,7 @@ def next_stage_proposals(proposal_deltas, proposals, box2box_weights, image_size
             d = proposal_deltas.detach().contiguous()
             buf, hold, _, n_chunks = _upload_table([(b, None, None, None, s) for b, s in zip(boxes, sizes)], dev)
             nbytes = L.lib().umr_box_decode_workspace(R, n_chunks)
-            ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
+            ws = T.workspace(nbytes, dev)
             T.timed(lambda _: L.check(L.lib().umr_box_decode(_p(buf), N, R, n_chunks, _p(d), T.dtype_code(d), *w, int(bool(training)), _p(out),
                                                              _p(keep), _p(counts), _p(ws), nbytes, _stream()), "umr_box_decode"),
                     (("decode", 1),), _phase_ms)
@@ -417,7 +417,7 @@ def fast_rcnn_losses(scores, proposal_deltas, proposals, *, box2box_weights, num
             table = [(b, gb, gc.to(torch.int64), gs, sz) for b, gb, gc, gs, sz in images]
             buf, hold, _, n_chunks = _upload_table(table, dev)
             nbytes = L.lib().umr_box_loss_workspace(n_chunks)
-            ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+            ws = T.workspace(nbytes, dev)
             w_in = None if weights is None else weights.detach().contiguous()
             sg = None if single is None else single.to(torch.float32).contiguous()
 

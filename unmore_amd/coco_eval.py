@@ -78,6 +78,7 @@ def _mask_iou_flat(units, device, what, prepared=None):
     U, K, P = len(prepared), int(start[-1]), int(pairs[-1])
     device = _device(device, what)
     from . import _lib as L
+    from ._tables import workspace
     from .ops import _p, _stream
     with torch.cuda.device(device):
         inter = torch.zeros(P, dtype=torch.int32, device=device)
@@ -100,7 +101,7 @@ def _mask_iou_flat(units, device, what, prepared=None):
             t_st, t_nd, t_po, t_cr = _dev(start, device), _dev(nd, device), _dev(pairs, device), _dev(crowd, device)
             st = torch.zeros(K, dtype=torch.int32, device=device)
             nbytes = L.lib().umr_mask_iou_workspace(K, total_chars, total_words)
-            ws = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device)
+            ws = workspace(nbytes, device)
             L.check(L.lib().umr_mask_iou(_p(chars), _p(t_co), K, total_chars, _p(t_us), _p(t_st), _p(t_nd), _p(t_po), _p(t_wo), _p(t_cr), U,
                                          max(h * w for _, (h, w), _, _ in prepared), int(nd.max()), int(ng.max()), P, total_words,
                                          _p(inter), _p(iou), _p(area), _p(st), _p(ws), nbytes, _stream()), "umr_mask_iou")

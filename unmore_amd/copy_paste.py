@@ -183,7 +183,7 @@ def copy_and_paste(labeled, unlabeled, params=None, *, rate=1.0, random_num=True
             res = torch.zeros(row_off * 6, dtype=torch.int32, device=dev)      # stats int32 [rows][2] | boxes f32 [rows][4]
             boxes_dev = res[row_off * 2:].view(torch.float32).view(row_off, 4)
             nbytes = L.lib().umr_copy_paste_workspace(word_off, inter_off)
-            ws = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=dev)
+            ws = T.workspace(nbytes, dev)
 
             def launch(phases):
                 L.check(L.lib().umr_copy_paste(_p(buf), len(active), _p(choice_dev), choice_off, word_off, inter_off, row_off, max_wpm, max_nc,

@@ -112,7 +112,7 @@ def select_detections(boxes, scores, image_shapes, score_thresh, nms_thresh, top
                "counts": torch.empty(N, dtype=torch.int32, device=dev), "first": first}
         buf = T.upload(tab, N, dev)[0]
         nbytes = L.lib().umr_det_select_workspace(N, cand, words)
-        ws = torch.empty((nbytes + 15) // 16 * 2, dtype=torch.int64, device=dev)
+        ws = T.workspace(nbytes, dev)
 
         def launch(phases):
             L.check(L.lib().umr_det_select(_p(buf), N, K, BC, cand, max_cand, words, out, st, nt, max(topk, -1), phases, _p(res["pred_boxes"]),

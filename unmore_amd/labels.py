@@ -4,6 +4,7 @@ pipeline per image on the host."""
 import torch
 
 from . import _lib as L
+from ._tables import upload, workspace
 from .ops import _p, _stream, _need_gpu
 
 
@@ -26,7 +27,7 @@ def synthesize_labels(masks, object_centers=None, use_bg_sdf=True):
     sal = torch.empty((B, H, W), dtype=torch.float32, device=dev)
     sdf = torch.empty((B, H, W), dtype=torch.float32, device=dev)
     ws_bytes = L.lib().umr_label_synthesis_workspace(B, H, W)
-    ws = torch.empty((ws_bytes + 3) // 4, dtype=torch.int32, device=dev)
+    ws = workspace(ws_bytes, dev)
     L.check(L.lib().umr_label_synthesis(_p(m8), _p(cen), _p(cf), _p(sal), _p(sdf), _p(ws), ws_bytes, B, H, W, int(bool(use_bg_sdf)),
                                         _stream()), "umr_label_synthesis")
     return {"center_field": cf, "saliency_mask": sal, "sdf": sdf}
@@ -101,7 +102,7 @@ def distance_transform(masks, normalize=True):
     B, H, W = m8.shape
     out = torch.empty((B, H, W), dtype=torch.float32, device=m8.device)
     nbytes = L.lib().umr_distance_transform_workspace(B, H, W)
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=m8.device)
+    ws = workspace(nbytes, m8.device)
     L.check(L.lib().umr_distance_transform(_p(m8), _p(out), _p(ws), nbytes, B, H, W, int(bool(normalize)), _stream()), "umr_distance_transform")
     return out
 
@@ -151,7 +152,7 @@ def synthesize_training_items(images, masks, image_size, scale=(0.08, 1.0), use_
     sal = torch.empty((B, S, S), dtype=torch.float32, device=dev)
     sdf = torch.empty((B, S, S), dtype=torch.float32, device=dev)
     nbytes = L.lib().umr_label_synthesis_workspace(B, S, S)
-    ws = torch.empty((nbytes + 3) // 4, dtype=torch.int32, device=dev)
+    ws = workspace(nbytes, dev)
     L.check(L.lib().umr_label_synthesis_cropped(_p(m_s), _p(centers), _p(fg_s), _p(cf), _p(sal), _p(sdf), _p(ws), nbytes, B, S, S,
                                                 int(bool(use_bg_sdf)), _stream()), "umr_label_synthesis_cropped")
     inst = m_s.float()
@@ -169,8 +170,6 @@ def synthesize_training_items(images, masks, image_size, scale=(0.08, 1.0), use_
 import random
 
 import numpy as np
-
-from ._tables import upload
 
 
 def _ragged_upload(f32s, u8s, shapes, extra, dev):
@@ -201,7 +200,7 @@ def background_squares(full_masks):
     tab, _ = _ragged_upload([None] * n, ms, shapes, [], dev)
     max_w, max_px = max(w for _, w in shapes), max(h * w for h, w in shapes)
     nbytes = L.lib().umr_bg_square_workspace(n, max_px)
-    ws = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+    ws = workspace(nbytes, dev)
     out5 = torch.empty((n, 5), dtype=torch.int32, device=dev)
     L.check(L.lib().umr_bg_square(_p(tab), _p(out5), _p(ws), nbytes, n, max_w, max_px, _stream()), "umr_bg_square")
     return out5

@@ -124,7 +124,7 @@ def _run(logits, images, classes, weights, side, max_h, max_w, dev, want_targets
             return loss, grad, counters, (None if targets is None else targets.view(torch.bool))
         buf, hold, _ = _upload_table(images, dev)
         nbytes = L.lib().umr_mask_loss_workspace(R, side)
-        ws = torch.empty(nbytes // 8, dtype=torch.int64, device=dev)
+        ws = T.workspace(nbytes, dev)
 
         def launch(phases):
             L.check(L.lib().umr_mask_loss(_p(buf), len(images), R, C, side, max_h, max_w, _p(logits), T.dtype_code(logits), _p(classes),

@@ -8,6 +8,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._tables import workspace
 from .ops import _p, _stream, _need_gpu
 
 
@@ -120,7 +121,7 @@ def nms(boxes, scores, iou_threshold):
     b = boxes.detach().to(torch.float32).contiguous()
     order = torch.sort(scores.detach().to(boxes.device), descending=True, stable=True).indices.contiguous()
     ws_bytes = int(L.lib().umr_nms_workspace(n))
-    ws = torch.empty(ws_bytes // 8, dtype=torch.int64, device=boxes.device)
+    ws = workspace(ws_bytes, boxes.device)
     keep = torch.empty(n, dtype=torch.int64, device=boxes.device)
     cnt = torch.zeros(1, dtype=torch.int32, device=boxes.device)
     L.check(L.lib().umr_nms(_p(b), _p(order), n, float(iou_threshold), _p(ws), ws_bytes, _p(keep), _p(cnt), _stream()), "umr_nms")

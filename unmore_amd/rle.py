@@ -318,6 +318,7 @@ def from_polygons(segmentations, sizes, device="cuda", phase_ms=None):
     if not polys:
         return []
     from . import _lib as L
+    from ._tables import workspace
     from .ops import _p, _stream
     host, (o_xy, o_po, o_ap, o_as, o_co), V, NP, NA, C = _poly_tables(polys, sizes)
     if C >= 1 << 31 or V >= 1 << 31:
@@ -326,7 +327,7 @@ def from_polygons(segmentations, sizes, device="cuda", phase_ms=None):
     with torch.cuda.device(device):
         buf = torch.from_numpy(host).to(device)
         nbytes = L.lib().umr_poly_rle_workspace(V, NP, NA, C)
-        ws = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device)
+        ws = workspace(nbytes, device)
         base = buf.data_ptr()
 
         def run(phases, sizes_t, offsets, chars, cap):
@@ -426,6 +427,7 @@ def _decode_call(records, groups, mode, device, what):
     if G == 0:
         return [], None
     from . import _lib as L
+    from ._tables import workspace
     from .ops import _stream
     device = torch.device(device)
     if device.type != "cuda":
@@ -455,7 +457,7 @@ def _decode_call(records, groups, mode, device, what):
         status = torch.empty(max(K, 1), dtype=torch.int32, device=device)
         info = torch.empty((G, 2), dtype=torch.int32, device=device) if mode == 1 else None
         nbytes = L.lib().umr_rle_decode_workspace(K, total_chars, total_segments, mode)
-        ws = torch.empty(nbytes // 8 + 1, dtype=torch.int64, device=device)
+        ws = workspace(nbytes, device)
         base = buf.data_ptr()
         vp = ctypes.c_void_p
         L.check(L.lib().umr_rle_decode(vp(base + o_chars), vp(base), K, total_chars, vp(base + o_desc), vp(base + o_gs), vp(base + o_seg), G,
