@@ -811,6 +811,38 @@ int umr_det_paste_rle(const void* logits, int dtype, int64_t N, int C, int M, co
                       const int32_t* frames, int frame_stride, float threshold, int64_t* sizes, const int64_t* offsets, uint8_t* chars,
                       int64_t chars_capacity, umr_stream_t stream);
 
+/* ---- the ROI pooler of the detector's heads (Detectron2's modeling/poolers.py ROIPooler with ROIAlignV2 = torchvision's
+ * roi_align(aligned=True); built at cad/modeling/roi_heads/custom_cascade_rcnn.py:117-122 and roi_heads.py:674-679, 709-716;
+ * csrc/roi_pool.hip) ---------------------------------------------------------------------------------------------------------------------
+ * R boxes, float32 XYXY in frame coordinates: rows of box_stride 4 ([R,4], in image order, with first int32 [N + 1] = the prefix sums of
+ * the boxes per image) or of box_stride 5 ([R,5] = image index as a float, then the box; first == NULL).  info int32 [R,2] = (image,
+ * level) per box, (-1, 0) for a box the device refuses: an image index outside [0, N) or not an integer, a coordinate that is not finite
+ * or beyond +-2^20.
+ * roi_pool_prepare writes info.  n_levels > 1: Detectron2's assign_boxes_to_levels in float32, operation by operation --
+ *   floor(canonical_level + log2(sqrt((x2 - x1) * (y2 - y1)) / canonical_box_size + 1e-8f)) clamped to [min_level, max_level], minus
+ *   min_level; a NaN (a negative area) gives level 0.  n_levels == 1: level 0.
+ * levels: a HOST array of 4 int64 per level, at most 8 levels, copied into the kernel's arguments by value (nothing is uploaded):
+ *   the pointer of the level's map [N,C,H,W] (UMR_F32 / UMR_BF16, contiguous), H, W, and the bits of the float32 scale (in (0, 16]).
+ * roi_pool_forward: out [R,C,P,P] in the maps' type = roi_align of box r on the map of its level and image, float32 arithmetic:
+ *   start = lo * scale - .5, roi = (hi * scale - .5) - start, bin = roi / P, grid = sampling_ratio or ceil(bin) when it is 0, a sample at
+ *   start + p * bin + (i + .5) * bin / grid, 0 outside [-1, size], clamped to [0, size - 1], bilinear taps, the mean over grid_h * grid_w.
+ *   Evaluated separably, sum_y Ay[ph,y] * (sum_x Ax[pw,x] * F[c,y,x]) / count with Ay, Ax the summed tap weights (csrc/roi_pool.hip).
+ *   A refused box, a level outside [0, n_levels) and roi <= 0 on an axis give a zero row.  One launch for all levels and images.
+ * roi_pool_backward: the pointers in levels are the GRADIENT maps, written whole (zeros included, no memset needed) with
+ *   grad[n,c,y,x] = the sum over the boxes r of image n and that level, in index order, ph outer and pw inner, of
+ *   ((Ay[ph,y] * Ax[pw,x]) / count_r) * grad_out[r,c,ph,pw]; a NULL pointer skips the level.  first: as above or NULL (then
+ *   every workgroup looks at all R rows).  No float atomics: the same input gives the same bytes on every run.
+ * 1 <= P <= 64; 0 <= sampling_ratio <= 1024; the two axis tables take 4 * (H + W) + 64 * P + 1112 bytes of LDS for the largest H and W, at
+ * most 64 KiB (else UMR_ERR_INVALID); the backward stages a box's output gradients there too, 128 * P * P bytes, when P <= 16 and they
+ * fit.  No synchronisation, nothing allocated. */
+int umr_roi_pool_prepare(const float* boxes, int box_stride, int64_t R, const int32_t* first, int64_t N, int n_levels, int min_level,
+                         int max_level, float canonical_box_size, int canonical_level, int32_t* info, umr_stream_t stream);
+int umr_roi_pool_forward(const int64_t* levels, int n_levels, int64_t N, int C, int dtype, const float* boxes, int box_stride,
+                         const int32_t* info, int64_t R, int P, int sampling_ratio, void* out, umr_stream_t stream);
+int umr_roi_pool_backward(const int64_t* levels, int n_levels, int64_t N, int C, int dtype, const float* boxes, int box_stride,
+                          const int32_t* info, const int32_t* first, int64_t R, int P, int sampling_ratio, const void* grad_out,
+                          umr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
