@@ -843,6 +843,31 @@ int umr_roi_pool_backward(const int64_t* levels, int n_levels, int64_t N, int C,
                           const int32_t* info, const int32_t* first, int64_t R, int P, int sampling_ratio, const void* grad_out,
                           umr_stream_t stream);
 
+/* ---- the RPN's proposal step (cad/modeling/meta_arch/rcnn.py:165, 213, 333 -> Detectron2's RPN.predict_proposals: _decode_proposals +
+ * find_top_rpn_proposals; csrc/rpn.hip) -------------------------------------------------------------------------------------------------
+ * levels: a HOST array of 5 int64 per level, at most 8 levels, copied into the kernels' arguments by value: the pointers of the level's
+ *   objectness logits [N,A,H,W] and anchor deltas [N,4A,H,W] (channel a * 4 + c; both UMR_F32 or both UMR_BF16, contiguous, read in
+ *   place), H, W and the stride (H * W * A < 2^31; H * stride, W * stride <= 2^24).  A <= 16.  cells: float32 [n_levels,16,4] on the device,
+ *   the cell anchors of level l in rows [0, A); image_sizes: float32 [N,2] = (h, w) on the device.
+ * Per (image, level): the K = min(H * W * A, pre_nms_topk) (<= 4096) largest logits over f = (y * W + x) * A + a in torch.topk's order
+ *   (NaN above +inf, -0.0 == +0.0), equal values in ascending f; anchor (x * stride + offset * stride, y * stride + offset * stride, ...) +
+ *   cell (offset * stride must be a float32 value); Box2BoxTransform.apply_deltas with weights (wx, wy, ww, wh); a candidate with a
+ *   non-finite coordinate or logit is dropped (flag 1); clip to (h, w); dropped unless x2 - x1 > min_box_size and y2 - y1 > min_box_size (flag 2); greedy NMS within the level in
+ *   that order (iou > nms_thresh, det_select's formula); the survivors of an image by descending logit, then level, then rank, the
+ *   first cap = min(post_nms_topk, sum of K) to out_boxes [N,cap,4] / out_logits [N,cap] (rows past counts[n] are NOT written).  The
+ *   float32 operation order is written out in csrc/rpn.hip.
+ * cand_* [N, sum of K] (boxes and raw x 4; raw may be NULL): every level's candidates in rank order, level after level: the clipped box,
+ *   the logit, f, the flag, and the box before the clip.  stats int32 [N,n_levels,5]: candidates, non-finite, empty, suppressed, kept by
+ *   the NMS.  phases: 1 = the partial selects of levels above 16384 scores, 2 = select + rank + decode, 4 = the suppression matrices,
+ *   8 = the scans, 16 = the merge; 31 = all (five launches).  workspace >= rpn_workspace(...) bytes, 16-byte aligned.  Nothing is read
+ *   back; no float atomics. */
+int64_t umr_rpn_workspace(const int64_t* levels, int n_levels, int64_t N, int A, int pre_nms_topk);
+int umr_rpn_proposals(const int64_t* levels, int n_levels, int64_t N, int A, int dtype, const float* cells, const float* image_sizes,
+                      int pre_nms_topk, int post_nms_topk, float nms_thresh, float min_box_size, float wx, float wy, float ww, float wh,
+                      double offset, int phases, float* cand_boxes, float* cand_scores, int32_t* cand_idx, uint8_t* cand_flags,
+                      float* cand_raw, float* out_boxes, float* out_logits, int32_t* counts, int32_t* stats, void* workspace,
+                      int64_t workspace_bytes, umr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

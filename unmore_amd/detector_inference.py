@@ -12,7 +12,7 @@ cad/evaluation/coco_evaluation.py:163-181, 398-457 (process, instances_to_coco_j
 Out of scope, on purpose:
   * averaging the cascade's stage scores (custom_cascade_rcnn.py:238-246): three softmaxes and two adds on [R, 2]; they stay torch ops
     in the caller, which hands the averaged `scores` and the last stage's `boxes` to fast_rcnn_inference;
-  * the RPN and the heads themselves (the pooler between them is unmore_amd.roi_pool);
+  * the heads themselves (the RPN's proposal step is unmore_amd.rpn, the pooler between them unmore_amd.roi_pool);
   * keypoints (`pred_keypoints` in instances_to_coco_json);
   * the soft-mask variant of paste_masks_in_image (mask_threshold < 0): masks are binary, threshold in [0.5, 1].
 
