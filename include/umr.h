@@ -868,6 +868,49 @@ int umr_rpn_proposals(const int64_t* levels, int n_levels, int64_t N, int A, int
                       float* cand_raw, float* out_boxes, float* out_logits, int32_t* counts, int32_t* stats, void* workspace,
                       int64_t workspace_bytes, umr_stream_t stream);
 
+/* ---- the RPN's training half (cad/modeling/meta_arch/rcnn.py:165, 333 -> Detectron2's RPN.label_and_sample_anchors and RPN.losses;
+ * csrc/rpn_loss.hip) -----------------------------------------------------------------------------------------------------------------------
+ * Anchors as above, never as a tensor: anchor r of an image = level after level, inside a level f = (y * W + x) * A + a; R per image
+ *   (R < 2^31 - 1).  cells: float32 [n_levels,16,4], image_sizes: float32 [N,2] = (h, w), gt_boxes: float32 [n_gt,4] = the images' ground
+ *   truths one after the other, gt_first: int32 [N+1] their prefix table; all on the device.
+ * rpn_label_sample, levels: a HOST array of 3 int64 per level (H, W, stride), by value into the kernels' arguments.
+ *   match   matched_vals / matched_idxs [N,R]: the maximum IoU (box_loss's formula: 0 unless inter > 0, correctly rounded division, bit
+ *           for bit a float32 NumPy value) over the image's ground truths and the FIRST index reaching it; row_max float32 [n_gt]: each
+ *           ground truth's maximum over the anchors (0 when it overlaps none).  A ground truth with a non-finite coordinate takes no part
+ *           and is counted (a departure from Detectron2, which would hand the NaN on).
+ *   label   labels int8 [N,R] BEFORE sampling: v < iou_lo: 0, v < iou_hi: -1, else 1; all 0 for an image without usable ground truths;
+ *           allow_low_quality: 1 as well where the anchor's IoU with some ground truth equals that row's maximum, exactly (the matched
+ *           index is not changed; a row maximum of 0 marks every anchor of IoU 0 with that ground truth: Detectron2's quirk);
+ *           boundary_thresh t >= 0: -1 unless x1 >= -t, y1 >= -t, x2 < w + t, y2 < h + t.
+ *   select  P, Q = the numbers of labels 1 and 0; num_pos = min(P, pos_cap), num_neg = min(Q, batch_size - num_pos); the num_pos (num_neg)
+ *           anchors of label 1 (0) with the largest key, equal keys to the lower r.  key = keys[n,r] & 0x7fffffff (keys int32 [N,R]) or,
+ *           keys == NULL, fmix(fmix(r ^ seed_lo) ^ (n * 0x9e3779b9 + seed_hi)) >> 1 with murmur3's 32-bit finaliser fmix and the halves
+ *           of seed.  sample_index int32 [N,batch_size]: r of the positives ascending, then of the negatives ascending; sample_gt: their
+ *           matched_idxs; counts int32 [N,2] = (num_pos, num_neg); entries past the counts are not written.  dense_labels int8 [N,R] or
+ *           NULL: the labels AFTER sampling (-1 for every anchor not sampled).
+ *   counters int32 [N,5]: P, Q, num_pos, num_neg, bad ground truths.  phases: 1 = match (zeroes counters and row_max first), 2 = label,
+ *   4 = the partial selects when R > 16384 (one workgroup per 16384 anchors, class and image), 8 = select; 15 = all (three or four
+ *   launches).  batch_size <= 1024.  workspace >= rpn_label_workspace(...) bytes (0 when R <= 16384), never NULL, 4-byte aligned.
+ * rpn_loss, levels: 7 int64 per level (H, W, stride, logits [N,A,H,W], deltas [N,4A,H,W], and the two gradient maps of the same shapes
+ *   and type, which the CALLER ZEROED: the launch stores only at the samples).  float64 arithmetic on the float32 anchors and widened
+ *   predictions: losses[0] = scale_cls * sum over the samples of binary_cross_entropy_with_logits(x, label), losses[1] = scale_loc * sum
+ *   over the sampled positives of smooth_l1(deltas - get_deltas(anchor, matched ground truth), beta) (beta < 1e-5: L1, gradient 0 at 0);
+ *   the gradient maps receive d losses[0] / d logits and d losses[1] / d deltas.  phases: 1 = terms, gradients and per-image partial
+ *   sums, 2 = the sum over the images in index order; 3 = all.  workspace >= rpn_loss_workspace(N) bytes, 8-byte aligned.
+ * No synchronisation, nothing read back, nothing allocated, no float atomics. */
+int64_t umr_rpn_label_workspace(const int64_t* levels, int n_levels, int64_t N, int A, int batch_size);
+int umr_rpn_label_sample(const int64_t* levels, int n_levels, int64_t N, int A, const float* cells, const float* image_sizes,
+                         const float* gt_boxes, const int32_t* gt_first, int64_t n_gt, float iou_lo, float iou_hi, int allow_low_quality,
+                         int batch_size, int pos_cap, float boundary_thresh, double offset, int64_t seed, const int32_t* keys, int phases,
+                         float* matched_vals, int32_t* matched_idxs, float* row_max, int8_t* labels, int32_t* sample_index,
+                         int32_t* sample_gt, int32_t* counts, int8_t* dense_labels, int32_t* counters, void* workspace,
+                         int64_t workspace_bytes, umr_stream_t stream);
+int64_t umr_rpn_loss_workspace(int64_t N);
+int umr_rpn_loss(const int64_t* levels, int n_levels, int64_t N, int A, int dtype, const float* cells, const float* gt_boxes,
+                 const int32_t* gt_first, int64_t n_gt, const int32_t* sample_index, const int32_t* sample_gt, const int32_t* counts,
+                 int batch_size, float wx, float wy, float ww, float wh, float smooth_l1_beta, double scale_cls, double scale_loc,
+                 double offset, int phases, float* losses, void* workspace, int64_t workspace_bytes, umr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,8 +25,8 @@ Limits (ValueError before any launch): at most 8 levels, A <= 16, pre_nms_topk <
 
 Out of scope, on purpose:
   * the RPN head's convolutions;
-  * anchor labelling / sampling and the RPN losses (they need a host-drawn permutation for subsample_labels, as INTEGRATION.md notes for
-    the ROI heads): the follow-up;
+  * anchor labelling / sampling and the RPN losses: they are unmore_amd.rpn_loss (subsample_labels' draw is a stateless hash key per
+    anchor there, or keys the caller supplies);
   * anchors that are not a regular grid, and rotated boxes;
   * graph-capture tests, as in the sibling modules.
 
