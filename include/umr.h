@@ -911,6 +911,34 @@ int umr_rpn_loss(const int64_t* levels, int n_levels, int64_t N, int A, int dtyp
                  int batch_size, float wx, float wy, float ww, float wh, float smooth_l1_beta, double scale_cls, double scale_loc,
                  double offset, int phases, float* losses, void* workspace, int64_t workspace_bytes, umr_stream_t stream);
 
+/* ---- the ROI heads' proposal sampling (cad/modeling/roi_heads/roi_heads.py:207-328 -> Detectron2's ROIHeads.label_and_sample_proposals
+ * with add_ground_truth_to_proposals, Matcher([t], [0, 1]) and subsample_labels; csrc/roi_sample.hip) -----------------------------------
+ * table: int64 [n_images,11] ON THE DEVICE, per image: the addresses of proposal_boxes float32 [R,4], objectness_logits float32 [R],
+ *   gt_boxes float32 [G,4], gt_classes int64 [G], gt_scores float32 [G] or 0, keys int32 [R+A] or 0; then R, G, A (G when the ground
+ *   truths are appended, else 0), chunk_first and cand_first.  Candidate r of an image: proposal r for r < R, ground truth r - R for
+ *   R <= r < R + A, read in place; R + A <= 16384.  The candidates of all images one after the other: n_cand in all, image n's at
+ *   cand_first, cut into chunks of 256 per image (chunk_first, n_chunks in all; an image without candidates shares its chunk_first with
+ *   the next one).
+ *   match   per candidate the maximum IoU (box_loss's formula, bit for bit a float32 NumPy value) over the image's ground truths and the
+ *           LOWEST index attaining it; a NaN never wins; foreground iff the maximum >= iou_threshold; class = gt_classes[matched] or
+ *           num_classes; an image without ground truths: all background, index 0.  A candidate with a non-finite coordinate is counted
+ *           (`bad`) and never sampled (a departure from Detectron2, whose Matcher would label the NaN row foreground).
+ *   select  subsample_labels: positive iff class != -1 and != num_classes, negative iff class == num_classes, P and Q of them; num_pos =
+ *           min(P, pos_cap), num_neg = min(Q, batch_size - num_pos); the num_pos (num_neg) candidates with the largest key, equal keys to
+ *           the lower r.  key = keys[r] & 0x7fffffff or, without keys, rpn_label_sample's hash of (seed, image, r); the caller salts the
+ *           seed.  Row order: the positives, then the negatives; inside each by_key ? (key descending, r ascending) : r ascending.
+ *   out_* [n_images,batch_size,...]: proposal boxes and logits (gt_logit for an appended ground truth), classes int64, the matched
+ *           ground truth's box and score (zero in an image without ground truths; out_gt_scores may be NULL) on EVERY row, the matched
+ *           index int64, the sampled r int32; rows past num_pos + num_neg are zero with class -1.  counts int32 [n_images,2] = (num_pos,
+ *           num_neg); counters int32 [n_images,5] = P, Q, num_pos, num_neg, bad.
+ *   phases: 1 = match, 2 = select + order + gather; 3 = all (two launches).  batch_size <= 1024.  workspace >= roi_sample_workspace(n_cand)
+ *   bytes, 4-byte aligned.  No synchronisation, nothing read back, nothing allocated, no atomics on memory: the same input, the same bytes. */
+int64_t umr_roi_sample_workspace(int64_t n_cand);
+int umr_roi_sample(const int64_t* table, int n_images, int64_t n_cand, int64_t n_chunks, float iou_threshold, int64_t num_classes,
+                   int batch_size, int pos_cap, int by_key, float gt_logit, int64_t seed, int phases, float* out_boxes, float* out_logits,
+                   int64_t* out_classes, float* out_gt_boxes, float* out_gt_scores, int64_t* out_matched_idxs, int32_t* out_sampled_idxs,
+                   int32_t* counts, int32_t* counters, void* workspace, int64_t workspace_bytes, umr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
