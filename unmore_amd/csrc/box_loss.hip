@@ -19,7 +19,7 @@
 //                      gradients and the seven counts; one partial per workgroup.
 //   bl_finish_kernel   sums the partials: the two losses as float32, the counts as int64.
 //
-// Arithmetic, float32, no contraction, every operation rounded on its own:
+// Arithmetic, float32, no contraction, every operation rounded on its own (det_box.h, shared with the other detector kernels):
 //   iou(a, b)   = inter > 0 ? inter / ((area_a + area_b) - inter) : 0,  inter = max(min(a.x2, b.x2) - max(a.x1, b.x1), 0) * (same in y),
 //                 area = (x2 - x1) * (y2 - y1); the division is correctly rounded, so the value equals a float32 NumPy restatement bit for bit.
 //   apply       w = x2 - x1; cx = x1 + .5 w; dx = dx / wx; dw = min(dw / ww, log(1000 / 16)); pcx = dx * w + cx; pw = expf(dw) * w;
@@ -27,6 +27,7 @@
 //   get         dx = wx * (tcx - scx) / sw; dw = ww * logf(tw / sw)   (Box2BoxTransform.get_deltas)
 #pragma clang fp contract(off)
 #include "umr_common.h"
+#include "det_box.h"
 #include <algorithm>
 #include <float.h>
 
@@ -35,9 +36,8 @@ namespace {
 constexpr int BL_THREADS = 256;
 constexpr int BL_GT_TILE = 256;                       // ground truths staged in LDS at a time (== BL_THREADS: one load per thread)
 constexpr int BL_UNIQUE_ROWS = 100;                   // the reference's gt_boxes.tensor[:100]
-constexpr float BL_SCALE_CLAMP = (float)4.135166556742356;   // log(1000 / 16) rounded to float32, as torch.clamp rounds the scalar
 
-struct BlW { float x, y, w, h; };                     // the Box2BoxTransform weights
+struct BlW { float v[4]; };                           // the Box2BoxTransform weights (wx, wy, ww, wh)
 
 static_assert(sizeof(umr_bl_image) == 56 && offsetof(umr_bl_image, width) == 52, "umr_bl_image is mirrored by _lib.BlImage");
 
@@ -58,52 +58,6 @@ __device__ __forceinline__ bool bl_entry_ok(const umr_bl_image& im, int chunk, i
     return im.R >= 0 && im.first >= 0 && im.first <= R - im.R && im.G >= 0 && chunk >= im.chunk_first &&
            (int64_t)(chunk - im.chunk_first) * BL_THREADS < im.R && im.boxes;
 }
-
-__device__ __forceinline__ bool bl_finite(float v) { return fabsf(v) <= FLT_MAX; }       // false for NaN and +-inf
-
-__device__ __forceinline__ float bl_area(float x1, float y1, float x2, float y2) { return (x2 - x1) * (y2 - y1); }
-
-__device__ __forceinline__ float bl_iou(float ax1, float ay1, float ax2, float ay2, float a_area, float bx1, float by1, float bx2, float by2,
-                                        float b_area) {
-    // torch.min / torch.max hand a NaN on (fminf / fmaxf would drop it): a NaN coordinate ends as inter > 0 == false, an IoU of 0
-    const float x_hi = (ax2 != ax2 || ax2 < bx2) ? ax2 : bx2, x_lo = (ax1 != ax1 || ax1 > bx1) ? ax1 : bx1;
-    const float y_hi = (ay2 != ay2 || ay2 < by2) ? ay2 : by2, y_lo = (ay1 != ay1 || ay1 > by1) ? ay1 : by1;
-    float w = x_hi - x_lo, h = y_hi - y_lo;
-    w = w > 0.f ? w : 0.f;
-    h = h > 0.f ? h : 0.f;
-    const float inter = w * h;
-    return inter > 0.f ? __fdiv_rn(inter, (a_area + b_area) - inter) : 0.f;
-}
-
-__device__ __forceinline__ void bl_apply(const float d[4], const float b[4], const BlW k, float out[4]) {
-    const float w = b[2] - b[0], h = b[3] - b[1];
-    const float cx = b[0] + .5f * w, cy = b[1] + .5f * h;
-    const float dx = __fdiv_rn(d[0], k.x), dy = __fdiv_rn(d[1], k.y);
-    float dw = __fdiv_rn(d[2], k.w), dh = __fdiv_rn(d[3], k.h);
-    dw = dw > BL_SCALE_CLAMP ? BL_SCALE_CLAMP : dw;                       // a NaN stays a NaN, as torch.clamp leaves it
-    dh = dh > BL_SCALE_CLAMP ? BL_SCALE_CLAMP : dh;
-    const float pcx = dx * w + cx, pcy = dy * h + cy;
-    const float pw = expf(dw) * w, ph = expf(dh) * h;
-    out[0] = pcx - .5f * pw;
-    out[1] = pcy - .5f * ph;
-    out[2] = pcx + .5f * pw;
-    out[3] = pcy + .5f * ph;
-}
-
-// false: an extent that Detectron2 would assert on (source) or take the logarithm of (target) is not positive, or something is not finite
-__device__ __forceinline__ bool bl_get(const float s[4], const float t[4], const BlW k, float out[4]) {
-    const float sw = s[2] - s[0], sh = s[3] - s[1];
-    const float scx = s[0] + .5f * sw, scy = s[1] + .5f * sh;
-    const float tw = t[2] - t[0], th = t[3] - t[1];
-    const float tcx = t[0] + .5f * tw, tcy = t[1] + .5f * th;
-    out[0] = __fdiv_rn(k.x * (tcx - scx), sw);
-    out[1] = __fdiv_rn(k.y * (tcy - scy), sh);
-    out[2] = k.w * logf(__fdiv_rn(tw, sw));
-    out[3] = k.h * logf(__fdiv_rn(th, sh));
-    return sw > 0.f && sh > 0.f && tw > 0.f && th > 0.f && bl_finite(out[0]) && bl_finite(out[1]) && bl_finite(out[2]) && bl_finite(out[3]);
-}
-
-__device__ __forceinline__ float bl_clip(float v, float hi) { return v < 0.f ? 0.f : (v > hi ? hi : v); }   // a NaN stays a NaN
 
 // the sum of v over the workgroup, in every thread; red: 4 ints of LDS
 __device__ __forceinline__ int bl_block_sum(int v, int* red) {
@@ -133,8 +87,8 @@ __global__ __launch_bounds__(BL_THREADS) void bl_match_kernel(const umr_bl_image
         const float* b = im.boxes + (int64_t)j * 4;
         p[0] = b[0]; p[1] = b[1]; p[2] = b[2]; p[3] = b[3];
     }
-    const bool bad = live && !(bl_finite(p[0]) && bl_finite(p[1]) && bl_finite(p[2]) && bl_finite(p[3]));
-    const float p_area = bl_area(p[0], p[1], p[2], p[3]);
+    const bool bad = live && !(box_finite(p[0]) && box_finite(p[1]) && box_finite(p[2]) && box_finite(p[3]));
+    const float p_area = box_area(p[0], p[1], p[2], p[3]);
     float best = -1.f;
     int best_g = 0;
     for (int g0 = 0; g0 < im.G; g0 += BL_GT_TILE) {
@@ -143,12 +97,12 @@ __global__ __launch_bounds__(BL_THREADS) void bl_match_kernel(const umr_bl_image
         if (tid < n) {
             const float* b = im.gt_boxes + (int64_t)(g0 + tid) * 4;
             gt[tid][0] = b[0]; gt[tid][1] = b[1]; gt[tid][2] = b[2]; gt[tid][3] = b[3];
-            gt[tid][4] = bl_area(b[0], b[1], b[2], b[3]);
+            gt[tid][4] = box_area(b[0], b[1], b[2], b[3]);
         }
         __syncthreads();
         if (live && !bad) {
             for (int g = 0; g < n; ++g) {
-                const float v = bl_iou(gt[g][0], gt[g][1], gt[g][2], gt[g][3], gt[g][4], p[0], p[1], p[2], p[3], p_area);
+                const float v = box_iou_match(gt[g][0], gt[g][1], gt[g][2], gt[g][3], gt[g][4], p[0], p[1], p[2], p[3], p_area);
                 // strict: the lowest index that attains the maximum.  A NaN (a ground truth that is not finite) never wins, where
                 // torch's max would hand it on: include/umr.h names the departure
                 if (v > best) { best = v; best_g = g0 + g; }
@@ -204,11 +158,11 @@ __global__ __launch_bounds__(BL_THREADS) void bl_decode_kernel(const umr_bl_imag
         const float box[4] = {b[0], b[1], b[2], b[3]};
         const float d[4] = {to_f32<T>(deltas[r * 4]), to_f32<T>(deltas[r * 4 + 1]), to_f32<T>(deltas[r * 4 + 2]), to_f32<T>(deltas[r * 4 + 3])};
         float o[4];
-        bl_apply(d, box, bw, o);
-        o[0] = bl_clip(o[0], im.width);
-        o[1] = bl_clip(o[1], im.height);
-        o[2] = bl_clip(o[2], im.width);
-        o[3] = bl_clip(o[3], im.height);
+        box_apply_deltas(d, box, bw.v, o);
+        o[0] = box_clip(o[0], im.width);
+        o[1] = box_clip(o[1], im.height);
+        o[2] = box_clip(o[2], im.width);
+        o[3] = box_clip(o[3], im.height);
         kept = !training || ((o[2] - o[0]) > 0.f && (o[3] - o[1]) > 0.f);
         tmp[r * 4] = o[0]; tmp[r * 4 + 1] = o[1]; tmp[r * 4 + 2] = o[2]; tmp[r * 4 + 3] = o[3];
         keep[r] = (uint8_t)kept;
@@ -262,7 +216,7 @@ __global__ __launch_bounds__(BL_THREADS) void bl_apply_kernel(const T* __restric
     const float box[4] = {boxes[r * 4], boxes[r * 4 + 1], boxes[r * 4 + 2], boxes[r * 4 + 3]};
     const float d[4] = {to_f32<T>(deltas[r * 4]), to_f32<T>(deltas[r * 4 + 1]), to_f32<T>(deltas[r * 4 + 2]), to_f32<T>(deltas[r * 4 + 3])};
     float o[4];
-    bl_apply(d, box, bw, o);
+    box_apply_deltas(d, box, bw.v, o);
     out[r * 4] = o[0]; out[r * 4 + 1] = o[1]; out[r * 4 + 2] = o[2]; out[r * 4 + 3] = o[3];
 }
 
@@ -273,7 +227,7 @@ __global__ __launch_bounds__(BL_THREADS) void bl_get_kernel(const float* __restr
     const float s[4] = {src[r * 4], src[r * 4 + 1], src[r * 4 + 2], src[r * 4 + 3]};
     const float t[4] = {target[r * 4], target[r * 4 + 1], target[r * 4 + 2], target[r * 4 + 3]};
     float o[4];
-    (void)bl_get(s, t, bw, o);                                              // the plain op returns what the arithmetic gives, NaN and inf included
+    (void)box_get_deltas(s, t, bw.v, o);                                    // the plain op returns what the arithmetic gives, NaN and inf included
     out[r * 4] = o[0]; out[r * 4 + 1] = o[1]; out[r * 4 + 2] = o[2]; out[r * 4 + 3] = o[3];
 }
 
@@ -304,7 +258,7 @@ __global__ __launch_bounds__(BL_THREADS) void bl_loss_kernel(const umr_bl_image*
         if (tid < m) {
             const float* b = im.gt_boxes + (int64_t)tid * 4;
             set[tid][0] = b[0]; set[tid][1] = b[1]; set[tid][2] = b[2]; set[tid][3] = b[3];
-            set[tid][4] = bl_area(b[0], b[1], b[2], b[3]);
+            set[tid][4] = box_area(b[0], b[1], b[2], b[3]);
         }
         __syncthreads();
         int first_of_its_kind = 0;
@@ -333,11 +287,11 @@ __global__ __launch_bounds__(BL_THREADS) void bl_loss_kernel(const umr_bl_image*
             w = weights_in[r];
         } else if (drop_mode == 2) {
             float o[4];
-            bl_apply(d, box, bw, o);                                        // the stage's own prediction, unclipped
-            const float o_area = bl_area(o[0], o[1], o[2], o[3]);
+            box_apply_deltas(d, box, bw.v, o);                              // the stage's own prediction, unclipped
+            const float o_area = box_area(o[0], o[1], o[2], o[3]);
             float iou_max = -1.f;
             for (int g = 0; g < n_set; ++g) {
-                const float v = bl_iou(o[0], o[1], o[2], o[3], o_area, set[g][0], set[g][1], set[g][2], set[g][3], set[g][4]);
+                const float v = box_iou_match(o[0], o[1], o[2], o[3], o_area, set[g][0], set[g][1], set[g][2], set[g][3], set[g][4]);
                 if (v > iou_max || v != v) iou_max = v;                     // torch.max: a NaN wins and stays
             }
             w = (iou_max <= iou_thresh) ? 0.f : 1.f;                        // 1 - (iou_max <= thresh): a NaN keeps the row
@@ -402,7 +356,7 @@ __global__ __launch_bounds__(BL_THREADS) void bl_loss_kernel(const umr_bl_image*
                 const float* gb = im.gt_boxes + (int64_t)j * 4;
                 const float tb[4] = {gb[0], gb[1], gb[2], gb[3]};
                 float t[4];
-                const bool ok = bl_get(box, tb, bw, t) && bl_finite(score);
+                const bool ok = box_get_deltas(box, tb, bw.v, t) && box_finite(score);
                 if (ok) {
                     float row = 0.f;
 #pragma unroll
@@ -474,7 +428,7 @@ int bl_check_table(const umr_bl_image* images, int n_images, int64_t R, int64_t 
 int bl_check_weights(float wx, float wy, float ww, float wh, BlW* out) {
     UMR_CHECK_ARG(wx > 0.f && wy > 0.f && ww > 0.f && wh > 0.f && wx <= FLT_MAX && wy <= FLT_MAX && ww <= FLT_MAX && wh <= FLT_MAX,
                   "box_loss: the box2box weights must be positive and finite");
-    *out = BlW{wx, wy, ww, wh};
+    *out = BlW{{wx, wy, ww, wh}};
     return UMR_OK;
 }
 

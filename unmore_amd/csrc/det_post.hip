@@ -16,8 +16,8 @@
 //   dp_scan_kernel        one wave per image walks the ranks in order; lane l holds words l and l + 64 of the removed set; a rank that is
 //                         not removed is kept and ORs its row into the set; stops at topk.  The kept ranks go through LDS and are written
 //                         by the whole wave: boxes, scores, classes, rows, and the count.
-// Arithmetic, float32, no contraction, every operation rounded on its own:
-//   clip        x < 0 ? 0 : (x > width ? width : x)          (a NaN stays a NaN, as in box_loss.hip; none arrives here)
+// Arithmetic, float32, no contraction, every operation rounded on its own (det_box.h: box_clip, box_area, box_iou_nms):
+//   clip        x < 0 ? 0 : (x > width ? width : x)          (a NaN stays a NaN; none arrives here)
 //   area        (x2 - x1) * (y2 - y1)
 //   iou(a, b)   w = max(0, min(a.x2, b.x2) - max(a.x1, b.x1)), h likewise, inter = w * h,
 //               iou = inter / ((area_a + area_b) - inter), correctly rounded; suppressed iff iou > nms_thresh (0 / 0 = NaN: not suppressed)
@@ -36,6 +36,7 @@
 // evaluated.  A box that is not finite or has x1 <= x0 or y1 <= y0 sets nothing.
 #pragma clang fp contract(off)
 #include "umr_common.h"
+#include "det_box.h"
 #include "rle_stream.h"
 #include <algorithm>
 #include <float.h>
@@ -52,8 +53,6 @@ static_assert(sizeof(umr_dp_image) == 48 && offsetof(umr_dp_image, mat_first) ==
 
 struct DpShape { int K, BC, max_cand, total_cand, total_out; long long total_words; };
 
-__device__ __forceinline__ bool dp_finite(float v) { return fabsf(v) <= FLT_MAX; }
-__device__ __forceinline__ float dp_clip(float v, float hi) { return v < 0.f ? 0.f : (v > hi ? hi : v); }
 __device__ __forceinline__ int dp_words(int n) { return (n + 63) >> 6; }
 
 // what the kernels trust of a table entry before they index with it
@@ -91,8 +90,8 @@ __global__ __launch_bounds__(DP_THREADS) void dp_candidates_kernel(const umr_dp_
             const float* b = im.boxes + (int64_t)r * bw;
             const float* s = im.scores + (int64_t)r * (K + 1);
             bool ok = true;
-            for (int q = 0; q < bw; ++q) ok = ok && dp_finite(b[q]);
-            for (int q = 0; q <= K; ++q) ok = ok && dp_finite(s[q]);
+            for (int q = 0; q < bw; ++q) ok = ok && box_finite(b[q]);
+            for (int q = 0; q <= K; ++q) ok = ok && box_finite(s[q]);
             sc = s[c];
             cand = ok && sc > score_thresh;
         }
@@ -110,6 +109,8 @@ __global__ __launch_bounds__(DP_THREADS) void dp_candidates_kernel(const umr_dp_
     }
     __syncthreads();
     if (tid == 0) ws.n_cand[k] = n;
+    // the rank count stands here and in rpn.hip's rpn_rank_kernel (on keys): moved into one inline function of det_box.h, this
+    // kernel compiled to other code (same registers, another schedule) that measured about 1 % slower on the MI355X
     const int n4 = n & ~3;
     for (int i = tid; i < n; i += DP_THREADS) {
         const float si = s_score[i];
@@ -125,7 +126,7 @@ __global__ __launch_bounds__(DP_THREADS) void dp_candidates_kernel(const umr_dp_
         }
         const int p = s_pair[i], r = p / K, c = p - r * K;
         const float* b = im.boxes + (int64_t)r * bw + (sh.BC == 1 ? 0 : c * 4);
-        const f32x4 box = {dp_clip(b[0], im.width), dp_clip(b[1], im.height), dp_clip(b[2], im.width), dp_clip(b[3], im.height)};
+        const f32x4 box = {box_clip(b[0], im.width), box_clip(b[1], im.height), box_clip(b[2], im.width), box_clip(b[3], im.height)};
         if (rank < n) {                                             // a permutation of [0, n): always
             const int64_t at = (int64_t)im.cand_first + rank;
             ws.sbox[at] = box;
@@ -155,15 +156,10 @@ __global__ __launch_bounds__(64) void dp_mask_kernel(const umr_dp_image* __restr
     if (i >= n) return;
     const f32x4 a = ws.sbox[cf + i];
     const int cls = ws.spair[cf + i] % sh.K;
-    const float a_area = (a[2] - a[0]) * (a[3] - a[1]);
+    const float a_area = box_area(a[0], a[1], a[2], a[3]);
     unsigned long long bits = 0ull;
     for (int jj = 0; jj < nj; ++jj) {
-        const f32x4 b = cbox[jj];
-        const float xx1 = fmaxf(a[0], b[0]), yy1 = fmaxf(a[1], b[1]), xx2 = fminf(a[2], b[2]), yy2 = fminf(a[3], b[3]);
-        const float w = fmaxf(0.f, xx2 - xx1), h = fmaxf(0.f, yy2 - yy1);
-        const float inter = w * h;
-        const float b_area = (b[2] - b[0]) * (b[3] - b[1]);
-        const float iou = __fdiv_rn(inter, (a_area + b_area) - inter);
+        const float iou = box_iou_nms(a, a_area, cbox[jj]);
         if (j0 + jj > i && ccls[jj] == cls && iou > nms_thresh) bits |= 1ull << jj;
     }
     ws.mat[im.mat_first + (int64_t)i * words + cb] = bits;
@@ -218,8 +214,8 @@ __global__ __launch_bounds__(DP_THREADS) void dp_scale_kernel(const float* __res
     if (i >= n) return;
     const float sx = rowinfo[i * 4], sy = rowinfo[i * 4 + 1];
     const float H = (float)((const int32_t*)rowinfo)[i * 4 + 2], W = (float)((const int32_t*)rowinfo)[i * 4 + 3];
-    const float x0 = dp_clip(boxes[i * 4] * sx, W), y0 = dp_clip(boxes[i * 4 + 1] * sy, H);
-    const float x1 = dp_clip(boxes[i * 4 + 2] * sx, W), y1 = dp_clip(boxes[i * 4 + 3] * sy, H);
+    const float x0 = box_clip(boxes[i * 4] * sx, W), y0 = box_clip(boxes[i * 4 + 1] * sy, H);
+    const float x1 = box_clip(boxes[i * 4 + 2] * sx, W), y1 = box_clip(boxes[i * 4 + 3] * sy, H);
     const float w = x1 - x0, h = y1 - y0;
     float* o = rec + (int64_t)i * 8;
     o[0] = x0; o[1] = y0; o[2] = x1; o[3] = y1; o[4] = w; o[5] = h;
@@ -267,10 +263,10 @@ __device__ __forceinline__ bool dp_paste_setup(const void* __restrict__ logits, 
     }
     const float x0 = box[0], y0 = box[1], x1 = box[2], y1 = box[3];
     ps = DpPaste{prob, M, x0, y0, x1, y1, thr, 0, 0, 0, 0};
-    if (ch < 0 || !(dp_finite(x0) && dp_finite(y0) && dp_finite(x1) && dp_finite(y1)) || !(x1 > x0 && y1 > y0)) return false;
+    if (ch < 0 || !(box_finite(x0) && box_finite(y0) && box_finite(x1) && box_finite(y1)) || !(x1 > x0 && y1 > y0)) return false;
     const float fW = (float)W, fH = (float)H;
-    const int xs = (int)floorf(dp_clip(x0, fW)), xe = (int)ceilf(dp_clip(x1, fW));
-    const int ys = (int)floorf(dp_clip(y0, fH)), ye = (int)ceilf(dp_clip(y1, fH));
+    const int xs = (int)floorf(box_clip(x0, fW)), xe = (int)ceilf(box_clip(x1, fW));
+    const int ys = (int)floorf(box_clip(y0, fH)), ye = (int)ceilf(box_clip(y1, fH));
     ps.vx = xs; ps.vy = ys; ps.vw = xe - xs; ps.vh = ye - ys;
     return ps.vw > 0 && ps.vh > 0;
 }

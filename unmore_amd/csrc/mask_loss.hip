@@ -41,6 +41,7 @@
 // (C > 1) is counted there too; it adds no loss, no count and a zero gradient, since no channel is its own.
 #pragma clang fp contract(off)
 #include "umr_common.h"
+#include "roi_align_axis.h"
 #include <algorithm>
 
 namespace {
@@ -61,30 +62,6 @@ inline int ml_slices(int M) { return (M * M + ML_THREADS - 1) / ML_THREADS; }   
 __host__ __device__ inline int64_t ml_lds_bytes(int M, int max_h, int max_w) {
     // 192 bytes of reduction scratch, 4 * M + 2 ints of runs, then the sample rows and columns
     return 200 + 16 * (int64_t)M + 8 * ((int64_t)ml_cap(max_h, M) + ml_cap(max_w, M));
-}
-
-__device__ __forceinline__ float ml_coord(float start, float bin, int grid, int p, int i) {
-    return start + (float)p * bin + __fdiv_rn(((float)i + .5f) * bin, (float)grid);
-}
-
-// the first i in [0, grid] with coordinate(p, i) >= bound (strict: > bound); the coordinate does not decrease with i
-__device__ __forceinline__ int ml_first(float start, float bin, int grid, int p, float bound, bool strict) {
-    int lo = 0, hi = grid;
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        const float c = ml_coord(start, bin, grid, p, mid);
-        if (strict ? c > bound : c >= bound) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
-
-// (low index, bits of the fraction), low = -1 for a sample outside [-1, size]
-__device__ __forceinline__ int2 ml_entry(float c, int size) {
-    if (!(c >= -1.f && c <= (float)size)) return make_int2(-1, 0);
-    if (c <= 0.f) c = 0.f;
-    int low = (int)c;
-    if (low >= size - 1) { low = size - 1; c = (float)low; }
-    return make_int2(low, __float_as_int(c - (float)low));
 }
 
 template <typename T, bool LOSS>
@@ -155,8 +132,8 @@ __global__ __launch_bounds__(ML_THREADS) void ml_main_kernel(const umr_ml_image*
             const int axis = k >= M, p = k - axis * M;
             const float start = axis ? start_w : start_h, bin = axis ? bin_w : bin_h;
             const int grid = axis ? grid_w : grid_h, size = axis ? W : H;
-            const int a = ml_first(start, bin, grid, p, -1.f, false);
-            const int b = max(a, ml_first(start, bin, grid, p, (float)size, true));
+            const int a = roi_axis_first(start, bin, grid, p, -1.f, false);
+            const int b = max(a, roi_axis_first(start, bin, grid, p, (float)size, true));
             lo_run[k] = a;
             off_run[axis * (M + 1) + p + 1] = b - a;
         }
@@ -179,9 +156,9 @@ __global__ __launch_bounds__(ML_THREADS) void ml_main_kernel(const umr_ml_image*
     if (sampled) {                                                      // workgroup-uniform
         for (int p = 0; p < M; ++p) {
             for (int k = tid; p >= ph0 && p < ph1 && k < off_h[p + 1] - off_h[p]; k += ML_THREADS)
-                ent_h[off_h[p] + k] = ml_entry(ml_coord(start_h, bin_h, grid_h, p, lo_run[p] + k), H);
+                ent_h[off_h[p] + k] = roi_axis_entry(roi_axis_coord(start_h, bin_h, grid_h, p, lo_run[p] + k), H);
             for (int k = tid; k < off_w[p + 1] - off_w[p]; k += ML_THREADS)
-                ent_w[off_w[p] + k] = ml_entry(ml_coord(start_w, bin_w, grid_w, p, lo_run[M + p] + k), W);
+                ent_w[off_w[p] + k] = roi_axis_entry(roi_axis_coord(start_w, bin_w, grid_w, p, lo_run[M + p] + k), W);
         }
         __syncthreads();
     }

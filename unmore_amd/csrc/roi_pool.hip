@@ -26,7 +26,7 @@
 //   coordinate(p, i) = start + p * bin + (i + .5f) * bin / grid;  outside [-1, size]: the sample adds 0.  Else c <= 0 -> 0; low = (int)c;
 //   low >= size - 1 -> low = high = size - 1, c = low; else high = low + 1;  l = c - low adds to tap `high`, h = 1 - l to tap `low`.
 // The coordinate does not decrease with i (a chain of monotone roundings), so the samples of a bin inside [-1, size] are one run, found
-// by bisection on the float32 expression itself (csrc/mask_loss.hip does the same), and their taps are the contiguous rows
+// by bisection on the float32 expression itself (roi_align_axis.h, shared with mask_loss.hip), and their taps are the contiguous rows
 // [tap_lo, tap_lo + n).  One thread walks one bin's run in sample order with the two open taps in registers, so Ay[ph, y] is the sum of
 // its weights in sample order.  The tables are compact: bin after bin, n weights each; neighbouring bins share at most a few rows, so an
 // axis takes at most size + 4 P + 8 floats whatever the box and whatever the grid -- both are walked by loops, neither is capped.
@@ -37,6 +37,7 @@
 // exactly 0 adds 0 whatever the map holds there.
 #pragma clang fp contract(off)
 #include "umr_common.h"
+#include "roi_align_axis.h"
 #include <algorithm>
 #include <string.h>
 
@@ -103,30 +104,6 @@ __device__ __forceinline__ RpGeom rp_geom(float x1, float y1, float x2, float y2
     return g;
 }
 
-__device__ __forceinline__ float rp_coord(float start, float bin, int grid, int p, int i) {
-    return start + (float)p * bin + __fdiv_rn(((float)i + .5f) * bin, (float)grid);
-}
-
-// the first i in [0, grid] with coordinate(p, i) >= bound (strict: > bound)
-__device__ __forceinline__ int rp_first(float start, float bin, int grid, int p, float bound, bool strict) {
-    int lo = 0, hi = grid;
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        const float c = rp_coord(start, bin, grid, p, mid);
-        if (strict ? c > bound : c >= bound) hi = mid; else lo = mid + 1;
-    }
-    return lo;
-}
-
-// (low tap, bits of the fraction), low = -1 for a sample outside [-1, size]; 0 <= low <= size - 1 otherwise
-__device__ __forceinline__ int2 rp_entry(float c, int size) {
-    if (!(c >= -1.f && c <= (float)size)) return make_int2(-1, 0);
-    if (c <= 0.f) c = 0.f;
-    int low = (int)c;
-    if (low >= size - 1) { low = size - 1; c = (float)low; }
-    return make_int2(low, __float_as_int(c - (float)low));
-}
-
 // views of the axis tables in LDS: index k = axis * P + p, axis 0 = rows against H, 1 = columns against W
 struct RpTables {
     int* run_a;      // [2P] first sample of the bin's run
@@ -156,11 +133,12 @@ __device__ bool rp_tables(const RpTables& t, const RpGeom& g, int P, int H, int 
         const int axis = k >= P, p = k - axis * P;
         const float start = axis ? g.start_w : g.start_h, bin = axis ? g.bin_w : g.bin_h;
         const int grid = axis ? g.grid_w : g.grid_h, size = axis ? W : H;
-        const int a = rp_first(start, bin, grid, p, -1.f, false);
-        const int b = max(a, rp_first(start, bin, grid, p, (float)size, true));
+        const int a = roi_axis_first(start, bin, grid, p, -1.f, false);
+        const int b = max(a, roi_axis_first(start, bin, grid, p, (float)size, true));
         int lo = 0, n = 0;
         if (b > a) {
-            const int2 e0 = rp_entry(rp_coord(start, bin, grid, p, a), size), e1 = rp_entry(rp_coord(start, bin, grid, p, b - 1), size);
+            const int2 e0 = roi_axis_entry(roi_axis_coord(start, bin, grid, p, a), size);
+            const int2 e1 = roi_axis_entry(roi_axis_coord(start, bin, grid, p, b - 1), size);
             if (e0.x >= 0 && e1.x >= e0.x) {
                 lo = e0.x;
                 n = e1.x + (e1.x < size - 1 ? 1 : 0) - lo + 1;
@@ -197,7 +175,7 @@ __device__ bool rp_tables(const RpTables& t, const RpGeom& g, int P, int H, int 
             if (j >= 0 && j < n) ent[j] = v;
         };
         for (int i = a; i < a + cnt; ++i) {
-            const int2 e = rp_entry(rp_coord(start, bin, grid, p, i), size);
+            const int2 e = roi_axis_entry(roi_axis_coord(start, bin, grid, p, i), size);
             if (e.x < 0) continue;
             const float l = __int_as_float(e.y), h = 1.f - l;
             if (e.x != cur) {

@@ -19,10 +19,11 @@
 //                      descending, r ascending); then the gathers, coalesced over (row, field), and the rows past the count: zero, class -1.
 //
 // Key of candidate r of image n (31 bits, 0 mapped to 1 so that 0 can mean "not in this pool"): keys[r] & 0x7fffffff when the image has
-// keys, else rpn_loss.hip's hash: fmix(fmix(r ^ s_lo) ^ (n * 0x9e3779b9 + s_hi)) >> 1 with murmur3's 32-bit finaliser and the halves of
-// the (salted, by the caller) seed.  IoU: box_loss.hip's bl_iou, float32, no contraction, every operation rounded on its own.
+// keys, else det_box.h's sample_key: fmix(fmix(r ^ s_lo) ^ (n * 0x9e3779b9 + s_hi)) >> 1 with murmur3's 32-bit finaliser and the halves of
+// the (salted, by the caller) seed.  IoU: det_box.h's box_iou_match, float32, no contraction, every operation rounded on its own.
 #pragma clang fp contract(off)
 #include "umr_common.h"
+#include "det_box.h"
 #include "select_in_order.h"
 #include <algorithm>
 #include <float.h>
@@ -79,28 +80,6 @@ __device__ __forceinline__ int rs_find(const int64_t* __restrict__ table, int n_
     return lo;
 }
 
-__device__ __forceinline__ bool rs_finite(float v) { return fabsf(v) <= FLT_MAX; }
-
-__device__ __forceinline__ float rs_area(float x1, float y1, float x2, float y2) { return (x2 - x1) * (y2 - y1); }
-
-// box_loss.hip's bl_iou
-__device__ __forceinline__ float rs_iou(float ax1, float ay1, float ax2, float ay2, float a_area, float bx1, float by1, float bx2, float by2,
-                                        float b_area) {
-    const float x_hi = (ax2 != ax2 || ax2 < bx2) ? ax2 : bx2, x_lo = (ax1 != ax1 || ax1 > bx1) ? ax1 : bx1;
-    const float y_hi = (ay2 != ay2 || ay2 < by2) ? ay2 : by2, y_lo = (ay1 != ay1 || ay1 > by1) ? ay1 : by1;
-    float w = x_hi - x_lo, h = y_hi - y_lo;
-    w = w > 0.f ? w : 0.f;
-    h = h > 0.f ? h : 0.f;
-    const float inter = w * h;
-    return inter > 0.f ? __fdiv_rn(inter, (a_area + b_area) - inter) : 0.f;
-}
-
-// rpn_loss.hip's rl_fmix
-__device__ __forceinline__ unsigned rs_fmix(unsigned h) {
-    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-    return h;
-}
-
 // candidate r of the image: a proposal, or an appended ground truth
 __device__ __forceinline__ const float* rs_candidate(const RsImage& im, int r) {
     return r < im.R ? im.boxes + (int64_t)r * 4 : im.gt_boxes + (int64_t)(r - im.R) * 4;
@@ -123,8 +102,8 @@ __global__ __launch_bounds__(RS_THREADS) void rs_match_kernel(const int64_t* __r
         const float* b = rs_candidate(im, r);
         p[0] = b[0]; p[1] = b[1]; p[2] = b[2]; p[3] = b[3];
     }
-    const bool bad = live && !(rs_finite(p[0]) && rs_finite(p[1]) && rs_finite(p[2]) && rs_finite(p[3]));
-    const float p_area = rs_area(p[0], p[1], p[2], p[3]);
+    const bool bad = live && !(box_finite(p[0]) && box_finite(p[1]) && box_finite(p[2]) && box_finite(p[3]));
+    const float p_area = box_area(p[0], p[1], p[2], p[3]);
     float best = -1.f;
     int best_g = 0;
     for (int g0 = 0; g0 < im.G; g0 += RS_GT_TILE) {
@@ -133,12 +112,12 @@ __global__ __launch_bounds__(RS_THREADS) void rs_match_kernel(const int64_t* __r
         if (tid < cnt) {
             const float* b = im.gt_boxes + (int64_t)(g0 + tid) * 4;
             gt[tid][0] = b[0]; gt[tid][1] = b[1]; gt[tid][2] = b[2]; gt[tid][3] = b[3];
-            gt[tid][4] = rs_area(b[0], b[1], b[2], b[3]);
+            gt[tid][4] = box_area(b[0], b[1], b[2], b[3]);
         }
         __syncthreads();
         if (live && !bad) {
             for (int g = 0; g < cnt; ++g) {
-                const float v = rs_iou(gt[g][0], gt[g][1], gt[g][2], gt[g][3], gt[g][4], p[0], p[1], p[2], p[3], p_area);
+                const float v = box_iou_match(gt[g][0], gt[g][1], gt[g][2], gt[g][3], gt[g][4], p[0], p[1], p[2], p[3], p_area);
                 if (v > best) { best = v; best_g = g0 + g; }              // strict: the lowest index that attains the maximum; a NaN never wins
             }
         }
@@ -154,7 +133,7 @@ __global__ __launch_bounds__(RS_THREADS) void rs_match_kernel(const int64_t* __r
         const long long c = im.gt_classes[best_g];
         pool = (c != -1 && c != num_classes) ? RS_POOL_POS : (c == num_classes ? RS_POOL_NEG : RS_POOL_NONE);
     }
-    unsigned k = im.keys ? (unsigned)im.keys[r] : rs_fmix(rs_fmix((unsigned)r ^ s_lo) ^ ((unsigned)n * 0x9e3779b9u + s_hi)) >> 1;
+    unsigned k = im.keys ? (unsigned)im.keys[r] : sample_key((unsigned)r, (unsigned)n, s_lo, s_hi);
     k &= 0x7fffffffu;
     const int64_t at = (int64_t)im.cand_first + r;
     midx[at] = best_g;
@@ -206,8 +185,9 @@ __global__ __launch_bounds__(RS_SELECT_THREADS) void rs_select_kernel(const int6
     __syncthreads();
     const int P = s_cnt[0], Q = s_cnt[1], n_bad = s_cnt[2];
     const int num_pos = min(P, pos_cap), num_neg = min(Q, B - num_pos), S = num_pos + num_neg;
-    if (num_pos > 0) (void)select_in_order(RsKeys{my_info, my_key, RS_POOL_POS}, (int64_t)C, num_pos, picked, hist, wtot);
-    if (num_neg > 0) (void)select_in_order(RsKeys{my_info, my_key, RS_POOL_NEG}, (int64_t)C, num_neg, picked + num_pos, hist, wtot);
+    const RsKeys pos_keys{my_info, my_key, RS_POOL_POS}, neg_keys{my_info, my_key, RS_POOL_NEG};
+    if (num_pos > 0) (void)select_in_order(pos_keys, (int64_t)C, num_pos, hist, wtot, SelectStoreIndex{picked});
+    if (num_neg > 0) (void)select_in_order(neg_keys, (int64_t)C, num_neg, hist, wtot, SelectStoreIndex{picked + num_pos});
     __syncthreads();
     if (by_key) {
         // each part is in ascending r: among equal keys the lower r is the lower position

@@ -6,9 +6,9 @@
 // Five launches for the whole batch, nothing read back, no float atomics (integer LDS atomics build histograms and counts: integer sums
 // have no order), the same input gives the same bytes.  The level descriptors travel in the kernels' arguments.
 //   rpn_part_kernel    one workgroup of 256 threads per (part, level, image), only for levels of more than RPN_SELECT_SHARE scores: the
-//                      top min(K, share) of the part's scores by a four-pass radix select over order-preserving keys, compacted IN f ORDER
-//                      (key and flat index f) into the workspace; the parts of a level lie one after the other, so their concatenation
-//                      is again in f order.
+//                      top min(K, share) of the part's scores by select_in_order.h's radix select over order-preserving keys, compacted
+//                      IN f ORDER (key and flat index f) into the workspace; the parts of a level lie one after the other, so their
+//                      concatenation is again in f order.
 //   rpn_rank_kernel    one workgroup of 1024 threads per (level, image): the same select over the level's scores (one part) or over its
 //                      parts' survivors, K of them in f order into LDS; every one counts its rank #{j : key_j > key_i or (key_j == key_i
 //                      and j < i)} (a permutation), decodes its anchor and writes the clipped box, the logit, f and a flag to rank's slot.
@@ -24,11 +24,12 @@
 //                      the levels' sorted lists); the first post_nms_topk are written.
 // Order of the scores: key(v) = 0xffffffff for a NaN; else with u = bits(v == 0 ? +0 : v): u < 0 ? ~u : u | 0x80000000.  Larger key =
 // larger value, a NaN above +inf, -0.0 == +0.0 (torch.topk's order); equal keys in ascending f = (y * W + x) * A + a.
-// Arithmetic, float32, no contraction, every operation rounded on its own:
+// Arithmetic, float32, no contraction, every operation rounded on its own (det_box.h: grid_anchor, box_apply_deltas, box_clip,
+// box_iou_nms):
 //   anchor      sx = float(x * stride) + off, sy = float(y * stride) + off  (off = offset * stride, exact);  (sx + c0, sy + c1, sx + c2, sy + c3)
 //               for the level's cell anchor c of index a
 //   apply       w = x2 - x1; cx = x1 + .5 w; dx = dx / wx; dw = min(dw / ww, log(1000 / 16)); pcx = dx * w + cx; pw = expf(dw) * w;
-//               x1' = pcx - .5 pw; x2' = pcx + .5 pw   (Box2BoxTransform.apply_deltas as box_loss.hip writes it; bfloat16 deltas widened)
+//               x1' = pcx - .5 pw; x2' = pcx + .5 pw   (Box2BoxTransform.apply_deltas; bfloat16 deltas widened)
 //   non-finite  a decoded coordinate or the logit is NaN or +-inf: dropped and counted (flag 1)
 //   clip        x < 0 ? 0 : (x > width ? width : x)
 //   empty       not (x2 - x1 > min_box_size and y2 - y1 > min_box_size) after the clip: dropped and counted (flag 2)
@@ -36,6 +37,8 @@
 //               iou = inter / ((area_a + area_b) - inter), correctly rounded; suppressed iff iou > nms_thresh (0 / 0 = NaN: not suppressed)
 #pragma clang fp contract(off)
 #include "umr_common.h"
+#include "det_box.h"
+#include "select_in_order.h"
 #include <algorithm>
 #include <float.h>
 #include <limits.h>
@@ -43,12 +46,13 @@
 namespace {
 
 constexpr int RPN_MAX_LEVELS = 8;
-constexpr int RPN_MAX_A = 16;
+constexpr int RPN_MAX_A = 16;                         // anchors per position the host accepts (rpn.py: MAX_ANCHORS)
 constexpr int RPN_MAX_K = 4096;                       // pre_nms_topk: 64 words of removed set = one per lane of the scanning wave
 constexpr int RPN_SELECT_SHARE = 16384;               // scores per workgroup of rpn_part_kernel
 constexpr int RPN_PART_THREADS = 256;
 constexpr int RPN_RANK_THREADS = 1024;
-constexpr float RPN_SCALE_CLAMP = (float)4.135166556742356;   // log(1000 / 16) rounded to float32
+
+static_assert(RPN_MAX_A == GRID_MAX_A, "the cells table [L, GRID_MAX_A, 4] has a row for every anchor the host accepts");
 
 struct RpnLevel {
     const void* logits;               // [N,A,H,W]
@@ -77,9 +81,6 @@ struct RpnWork {
     f32x4* kbox; float* kscore; int32_t* nkept;       // [N, cand_total], [N, L]
 };
 
-__device__ __forceinline__ bool rpn_finite(float v) { return fabsf(v) <= FLT_MAX; }
-__device__ __forceinline__ float rpn_clip(float v, float hi) { return v < 0.f ? 0.f : (v > hi ? hi : v); }
-
 __device__ __forceinline__ unsigned rpn_key(float v) {
     if (v != v) return 0xffffffffu;
     if (v == 0.f) return 0x80000000u;
@@ -103,65 +104,12 @@ struct RpnSrc {
     __device__ __forceinline__ int idx(int i) const { return pkey ? pidx[i] : f0 + i; }
 };
 
-// The k largest keys of src[0, n) (1 <= k <= n), equal keys in sequence order, written in sequence order to out_key / out_idx [k].
-// Every thread of the workgroup calls it; hist: 256 ints, wtot: 2 * 16 ints of LDS.
-__device__ void rpn_select(const RpnSrc& src, int n, int k, unsigned* out_key, int32_t* out_idx, int* hist, int* wtot) {
-    const int tid = threadIdx.x, T = blockDim.x, lane = tid & 63, wv = tid >> 6, nw = T >> 6;
-    unsigned prefix = 0u, mask = 0u;
-    int remaining = k;
-    for (int shift = 24; shift >= 0; shift -= 8) {
-        __syncthreads();
-        for (int b = tid; b < 256; b += T) hist[b] = 0;
-        __syncthreads();
-        for (int i = tid; i < n; i += T) {
-            const unsigned key = src.key(i);
-            if ((key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1);
-        }
-        __syncthreads();
-        int cum = 0, digit = 0;
-        for (int b = 255; b >= 0; --b) {                            // every thread walks the same histogram
-            const int h = hist[b];
-            if (cum + h >= remaining) { digit = b; break; }
-            cum += h;
-        }
-        remaining -= cum;
-        prefix |= (unsigned)digit << shift;
-        mask |= 255u << shift;
-    }
-    // prefix: the k-th largest key; remaining >= 1 of the keys equal to it are taken, the first ones
-    int n_gt = 0, n_eq = 0, par = 0;
-    for (int base = 0; base < n; base += T) {
-        const int i = base + tid;
-        bool gt = false, eq = false;
-        if (i < n) {
-            const unsigned key = src.key(i);
-            gt = key > prefix;
-            eq = key == prefix;
-        }
-        const unsigned long long vg = __ballot(gt), ve = __ballot(eq);
-        if (lane == 0) wtot[par * 16 + wv] = __popcll(vg) | (__popcll(ve) << 8);
-        __syncthreads();
-        const unsigned long long below = (1ull << lane) - 1ull;
-        int g = n_gt + __popcll(vg & below), e = n_eq + __popcll(ve & below), tg = 0, te = 0;
-        for (int w = 0; w < nw; ++w) {
-            const int v = wtot[par * 16 + w];
-            if (w < wv) { g += v & 255; e += v >> 8; }
-            tg += v & 255;
-            te += v >> 8;
-        }
-        if (gt || (eq && e < remaining)) {
-            const int at = g + min(e, remaining);
-            if (at < k) {                                           // always
-                out_key[at] = gt ? src.key(i) : prefix;
-                out_idx[at] = src.idx(i);
-            }
-        }
-        n_gt += tg;
-        n_eq += te;
-        par ^= 1;
-    }
-    __syncthreads();
-}
+// what a select of the scores keeps of its j-th entry: the key and the flat index f.  rpn_key never returns 0 (a NaN maps to
+// 0xffffffff, +-0 to 0x80000000, a negative to ~u >= 0x007fffff), so select_in_order's "key 0 takes no part" cannot drop a score.
+struct RpnKeep {
+    const RpnSrc& src; unsigned* key; int32_t* idx;
+    __device__ __forceinline__ void operator()(int j, int i, unsigned k) const { key[j] = k; idx[j] = src.idx(i); }
+};
 
 __global__ __launch_bounds__(RPN_PART_THREADS) void rpn_part_kernel(RpnPlan pl, RpnWork ws) {
     __shared__ int hist[256];
@@ -172,7 +120,7 @@ __global__ __launch_bounds__(RPN_PART_THREADS) void rpn_part_kernel(RpnPlan pl, 
     const int f0 = part * RPN_SELECT_SHARE, cnt = min(RPN_SELECT_SHARE, lv.n - f0), k = min(lv.K, cnt);
     const RpnSrc src{lv.logits, pl.dtype, pl.A, lv.H * lv.W, (int64_t)n * pl.A * lv.H * lv.W, f0, nullptr, nullptr};
     const long long at = (long long)n * pl.part_total + lv.part_first + (long long)part * lv.K;
-    rpn_select(src, cnt, k, ws.pkey + at, ws.pidx + at, hist, wtot);
+    (void)select_in_order(src, cnt, k, hist, wtot, RpnKeep{src, ws.pkey + at, ws.pidx + at});
 }
 
 __global__ __launch_bounds__(RPN_RANK_THREADS) void rpn_rank_kernel(RpnPlan pl, RpnWork ws, const float* __restrict__ cells,
@@ -194,18 +142,18 @@ __global__ __launch_bounds__(RPN_RANK_THREADS) void rpn_rank_kernel(RpnPlan pl, 
     if (tid < 2) s_bad[tid] = 0;
     if (lv.parts <= 1) {
         const RpnSrc src{lv.logits, pl.dtype, pl.A, HW, img, 0, nullptr, nullptr};
-        rpn_select(src, lv.n, K, s_key, s_idx, hist, wtot);
+        (void)select_in_order(src, lv.n, K, hist, wtot, RpnKeep{src, s_key, s_idx});
     } else {
         const long long at = (long long)n * pl.part_total + lv.part_first;
         const RpnSrc src{nullptr, 0, 1, 1, 0, 0, ws.pkey + at, ws.pidx + at};
-        rpn_select(src, lv.part_len, K, s_key, s_idx, hist, wtot);
+        (void)select_in_order(src, lv.part_len, K, hist, wtot, RpnKeep{src, s_key, s_idx});
     }
     const float height = image_sizes[n * 2], width = image_sizes[n * 2 + 1];
     const int64_t cb = (int64_t)n * pl.cand_total + lv.cand_first;
     const int K4 = K & ~3;
     for (int i = tid; i < K; i += RPN_RANK_THREADS) {
         const unsigned ki = s_key[i];
-        int rank = 0;
+        int rank = 0;                                               // det_post.hip's dp_candidates_kernel counts the same on scores
         for (int j = 0; j < K4; j += 4) {
             const u32x4 v = *(const u32x4*)(s_key + j);
             rank += (v[0] > ki || (v[0] == ki && j < i)) + (v[1] > ki || (v[1] == ki && j + 1 < i)) +
@@ -218,24 +166,17 @@ __global__ __launch_bounds__(RPN_RANK_THREADS) void rpn_rank_kernel(RpnPlan pl, 
         int f = s_idx[i];
         if (f < 0 || f >= lv.n) f = 0;                              // never: the indices are this call's own
         const int pix = f / pl.A, a = f - pix * pl.A, y = pix / lv.W, x = pix - y * lv.W;
-        const float* c = cells + (l * RPN_MAX_A + a) * 4;
-        const float sx = (float)(x * lv.stride) + lv.off, sy = (float)(y * lv.stride) + lv.off;
-        const float b0 = sx + c[0], b1 = sy + c[1], b2 = sx + c[2], b3 = sy + c[3];
+        const float wt[4] = {bw[0], bw[1], bw[2], bw[3]};           // here, not before the loop: there it cost the rank count its schedule
+        float anchor[4], r[4];
+        grid_anchor(cells + (l * GRID_MAX_A + a) * 4, x, y, lv.stride, lv.off, anchor);
         const int64_t dat = (int64_t)n * 4 * pl.A * HW + (int64_t)(a * 4) * HW + pix;
-        const float d0 = rpn_load(lv.deltas, pl.dtype, dat), d1 = rpn_load(lv.deltas, pl.dtype, dat + HW);
-        const float d2 = rpn_load(lv.deltas, pl.dtype, dat + 2 * (int64_t)HW), d3 = rpn_load(lv.deltas, pl.dtype, dat + 3 * (int64_t)HW);
+        const float d[4] = {rpn_load(lv.deltas, pl.dtype, dat), rpn_load(lv.deltas, pl.dtype, dat + HW),
+                            rpn_load(lv.deltas, pl.dtype, dat + 2 * (int64_t)HW), rpn_load(lv.deltas, pl.dtype, dat + 3 * (int64_t)HW)};
         const float score = rpn_load(lv.logits, pl.dtype, img + (int64_t)a * HW + pix);
-        const float w = b2 - b0, h = b3 - b1;
-        const float cx = b0 + .5f * w, cy = b1 + .5f * h;
-        const float dx = __fdiv_rn(d0, bw[0]), dy = __fdiv_rn(d1, bw[1]);
-        float dw = __fdiv_rn(d2, bw[2]), dh = __fdiv_rn(d3, bw[3]);
-        dw = dw > RPN_SCALE_CLAMP ? RPN_SCALE_CLAMP : dw;           // a NaN stays a NaN
-        dh = dh > RPN_SCALE_CLAMP ? RPN_SCALE_CLAMP : dh;
-        const float pcx = dx * w + cx, pcy = dy * h + cy;
-        const float pw = expf(dw) * w, ph = expf(dh) * h;
-        const f32x4 raw = {pcx - .5f * pw, pcy - .5f * ph, pcx + .5f * pw, pcy + .5f * ph};
-        const bool fin = rpn_finite(raw[0]) && rpn_finite(raw[1]) && rpn_finite(raw[2]) && rpn_finite(raw[3]) && rpn_finite(score);
-        const f32x4 box = {rpn_clip(raw[0], width), rpn_clip(raw[1], height), rpn_clip(raw[2], width), rpn_clip(raw[3], height)};
+        box_apply_deltas(d, anchor, wt, r);
+        const f32x4 raw = {r[0], r[1], r[2], r[3]};
+        const bool fin = box_finite(raw[0]) && box_finite(raw[1]) && box_finite(raw[2]) && box_finite(raw[3]) && box_finite(score);
+        const f32x4 box = {box_clip(raw[0], width), box_clip(raw[1], height), box_clip(raw[2], width), box_clip(raw[3], height)};
         const bool full = (box[2] - box[0] > min_box_size) && (box[3] - box[1] > min_box_size);
         const int flag = !fin ? 1 : (!full ? 2 : 0);
         if (rank < K) {                                             // a permutation of [0, K): always
@@ -266,15 +207,11 @@ __global__ __launch_bounds__(64) void rpn_mask_kernel(RpnPlan pl, RpnWork ws, fl
     const int i = rb * 64 + t;
     if (i >= K) return;
     const f32x4 a = cbox[cb + i];
-    const float a_area = (a[2] - a[0]) * (a[3] - a[1]);
+    const float a_area = box_area(a[0], a[1], a[2], a[3]);
     unsigned long long bits = 0ull;
     for (int jj = 0; jj < nj; ++jj) {
         const f32x4 b = tile[jj];
-        const float xx1 = fmaxf(a[0], b[0]), yy1 = fmaxf(a[1], b[1]), xx2 = fminf(a[2], b[2]), yy2 = fminf(a[3], b[3]);
-        const float w = fmaxf(0.f, xx2 - xx1), h = fmaxf(0.f, yy2 - yy1);
-        const float inter = w * h;
-        const float b_area = (b[2] - b[0]) * (b[3] - b[1]);
-        const float iou = __fdiv_rn(inter, (a_area + b_area) - inter);
+        const float iou = box_iou_nms(a, a_area, b);
         if (j0 + jj > i && iou > nms_thresh) bits |= 1ull << jj;
     }
     ws.mat[(long long)n * pl.mat_total + lv.mat_first + (long long)i * words + cbk] = bits;

@@ -30,10 +30,10 @@
 //
 // Key of anchor r of image n (31 bits): keys[n, r] & 0x7fffffff when keys are given, else with s_lo / s_hi the low / high 32 bits of seed
 //   fmix(h): h ^= h >> 16; h *= 0x85ebca6b; h ^= h >> 13; h *= 0xc2b2ae35; h ^= h >> 16          (murmur3's 32-bit finaliser, mod 2^32)
-//   key = fmix(fmix(r ^ s_lo) ^ (n * 0x9e3779b9 + s_hi)) >> 1
+//   key = fmix(fmix(r ^ s_lo) ^ (n * 0x9e3779b9 + s_hi)) >> 1                                    (det_box.h's sample_key)
 // Arithmetic.  Matching and labelling: float32, no contraction, every operation rounded on its own:
 //   anchor      sx = float(x * stride) + off, sy = float(y * stride) + off (off = offset * stride, exact); (sx + c0, sy + c1, sx + c2, sy + c3)
-//   iou(a, b)   = inter > 0 ? inter / ((area_a + area_b) - inter) : 0, box_loss.hip's bl_iou, the division correctly rounded
+//   iou(a, b)   = inter > 0 ? inter / ((area_a + area_b) - inter) : 0, det_box.h's box_iou_match, the division correctly rounded
 // Losses: float64 on the float32 anchors, ground truths and widened predictions (at most B samples per image; with smooth_l1_beta > 0
 // the gradient (p - t) / beta would otherwise carry t's float32 rounding relative to a difference that can be small):
 //   cls         max(x, 0) - x t + log1p(exp(-|x|)); d/dx = t ? -1 / (1 + exp(x)) : 1 / (1 + exp(-x))   (sigmoid(x) - t without cancellation)
@@ -42,6 +42,7 @@
 //   both sums times their scale = loss_weight / (B * N); the gradients times the same scale, rounded once to the inputs' type.
 #pragma clang fp contract(off)
 #include "umr_common.h"
+#include "det_box.h"
 #include "select_in_order.h"
 #include <algorithm>
 #include <float.h>
@@ -50,7 +51,6 @@
 namespace {
 
 constexpr int RL_MAX_LEVELS = 8;
-constexpr int RL_MAX_A = 16;
 constexpr int RL_MAX_BATCH = 1024;
 constexpr int RL_THREADS = 256;
 constexpr int RL_GT_TILE = 256;                       // == RL_THREADS: one load per thread
@@ -77,22 +77,6 @@ struct RlPlan {
 
 using Partial = SumPartial<2, 1>;     // per image: the objectness and the localisation sum; the samples
 
-__device__ __forceinline__ bool rl_finite(float v) { return fabsf(v) <= FLT_MAX; }
-
-__device__ __forceinline__ float rl_area(float x1, float y1, float x2, float y2) { return (x2 - x1) * (y2 - y1); }
-
-// box_loss.hip's bl_iou
-__device__ __forceinline__ float rl_iou(float ax1, float ay1, float ax2, float ay2, float a_area, float bx1, float by1, float bx2, float by2,
-                                        float b_area) {
-    const float x_hi = (ax2 != ax2 || ax2 < bx2) ? ax2 : bx2, x_lo = (ax1 != ax1 || ax1 > bx1) ? ax1 : bx1;
-    const float y_hi = (ay2 != ay2 || ay2 < by2) ? ay2 : by2, y_lo = (ay1 != ay1 || ay1 > by1) ? ay1 : by1;
-    float w = x_hi - x_lo, h = y_hi - y_lo;
-    w = w > 0.f ? w : 0.f;
-    h = h > 0.f ? h : 0.f;
-    const float inter = w * h;
-    return inter > 0.f ? __fdiv_rn(inter, (a_area + b_area) - inter) : 0.f;
-}
-
 struct RlAt { int l, a, pix; };       // where anchor r sits: level, cell anchor, y * W + x
 
 __device__ __forceinline__ RlAt rl_locate(const RlPlan& pl, int r) {
@@ -105,14 +89,7 @@ __device__ __forceinline__ RlAt rl_locate(const RlPlan& pl, int r) {
 __device__ __forceinline__ void rl_anchor(const RlPlan& pl, const float* __restrict__ cells, const RlAt at, float b[4]) {
     const RlLevel& lv = pl.lv[at.l];
     const int y = at.pix / lv.W, x = at.pix - y * lv.W;
-    const float* c = cells + (at.l * RL_MAX_A + at.a) * 4;
-    const float sx = (float)(x * lv.stride) + lv.off, sy = (float)(y * lv.stride) + lv.off;
-    b[0] = sx + c[0]; b[1] = sy + c[1]; b[2] = sx + c[2]; b[3] = sy + c[3];
-}
-
-__device__ __forceinline__ unsigned rl_fmix(unsigned h) {
-    h ^= h >> 16; h *= 0x85ebca6bu; h ^= h >> 13; h *= 0xc2b2ae35u; h ^= h >> 16;
-    return h;
+    grid_anchor(cells + (at.l * GRID_MAX_A + at.a) * 4, x, y, lv.stride, lv.off, b);
 }
 
 // the image's ground truths [g_lo, g_lo + G), trusted only as far as the table is ordered
@@ -137,7 +114,7 @@ __global__ __launch_bounds__(RL_THREADS) void rl_match_kernel(RlPlan pl, const f
     rl_gt_range(gt_first, n, n_gt, g_lo, G);
     float p[4] = {0.f, 0.f, 0.f, 0.f};
     if (live) rl_anchor(pl, cells, rl_locate(pl, r), p);
-    const float p_area = rl_area(p[0], p[1], p[2], p[3]);
+    const float p_area = box_area(p[0], p[1], p[2], p[3]);
     if (tid == 0) s_bad = 0;
     float best = -1.f;
     int best_g = 0;
@@ -146,9 +123,9 @@ __global__ __launch_bounds__(RL_THREADS) void rl_match_kernel(RlPlan pl, const f
         __syncthreads();
         if (tid < cnt) {
             const float* b = gt_boxes + (int64_t)(g_lo + g0 + tid) * 4;
-            const bool fin = rl_finite(b[0]) && rl_finite(b[1]) && rl_finite(b[2]) && rl_finite(b[3]);
+            const bool fin = box_finite(b[0]) && box_finite(b[1]) && box_finite(b[2]) && box_finite(b[3]);
             gt[tid][0] = b[0]; gt[tid][1] = b[1]; gt[tid][2] = b[2]; gt[tid][3] = b[3];
-            gt[tid][4] = rl_area(b[0], b[1], b[2], b[3]);
+            gt[tid][4] = box_area(b[0], b[1], b[2], b[3]);
             ok[tid] = fin;
             smax[tid] = 0u;
             if (!fin) atomicAdd(&s_bad, 1);
@@ -157,7 +134,7 @@ __global__ __launch_bounds__(RL_THREADS) void rl_match_kernel(RlPlan pl, const f
         if (live) {
             for (int g = 0; g < cnt; ++g) {
                 if (!ok[g]) continue;
-                const float v = rl_iou(gt[g][0], gt[g][1], gt[g][2], gt[g][3], gt[g][4], p[0], p[1], p[2], p[3], p_area);
+                const float v = box_iou_match(gt[g][0], gt[g][1], gt[g][2], gt[g][3], gt[g][4], p[0], p[1], p[2], p[3], p_area);
                 if (v > best) { best = v; best_g = g0 + g; }              // strict: the first index that reaches the maximum
                 if (v > 0.f) {
                     const unsigned bits = __float_as_uint(v);             // v > 0: the bits order as the values do
@@ -192,7 +169,7 @@ __global__ __launch_bounds__(RL_THREADS) void rl_label_kernel(RlPlan pl, const f
     const int usable = G - counters[n * RL_COUNTERS + 4];                 // the match launch left the number of bad ground truths there
     float p[4] = {0.f, 0.f, 0.f, 0.f};
     if (live) rl_anchor(pl, cells, rl_locate(pl, r), p);
-    const float p_area = rl_area(p[0], p[1], p[2], p[3]);
+    const float p_area = box_area(p[0], p[1], p[2], p[3]);
     if (tid < 2) s_cnt[tid] = 0;
     int label = 0;
     if (live && usable > 0) {
@@ -206,15 +183,15 @@ __global__ __launch_bounds__(RL_THREADS) void rl_label_kernel(RlPlan pl, const f
             if (tid < cnt) {
                 const float* b = gt_boxes + (int64_t)(g_lo + g0 + tid) * 4;
                 gt[tid][0] = b[0]; gt[tid][1] = b[1]; gt[tid][2] = b[2]; gt[tid][3] = b[3];
-                gt[tid][4] = rl_area(b[0], b[1], b[2], b[3]);
+                gt[tid][4] = box_area(b[0], b[1], b[2], b[3]);
                 gt[tid][5] = __uint_as_float(row_max[g_lo + g0 + tid]);
-                ok[tid] = rl_finite(b[0]) && rl_finite(b[1]) && rl_finite(b[2]) && rl_finite(b[3]);
+                ok[tid] = box_finite(b[0]) && box_finite(b[1]) && box_finite(b[2]) && box_finite(b[3]);
             }
             __syncthreads();
             if (live && label != 1) {
                 for (int g = 0; g < cnt; ++g) {
                     if (!ok[g]) continue;
-                    const float v = rl_iou(gt[g][0], gt[g][1], gt[g][2], gt[g][3], gt[g][4], p[0], p[1], p[2], p[3], p_area);
+                    const float v = box_iou_match(gt[g][0], gt[g][1], gt[g][2], gt[g][3], gt[g][4], p[0], p[1], p[2], p[3], p_area);
                     if (v == gt[g][5]) { label = 1; break; }
                 }
             }
@@ -242,7 +219,7 @@ __global__ __launch_bounds__(RL_THREADS) void rl_label_kernel(RlPlan pl, const f
 struct RlKeys {
     const int8_t* labels; const int32_t* keys; int want; unsigned s_lo, mix;
     __device__ __forceinline__ unsigned of(int r) const {
-        const unsigned k = keys ? (unsigned)keys[r] : rl_fmix(rl_fmix((unsigned)r ^ s_lo) ^ mix) >> 1;
+        const unsigned k = keys ? (unsigned)keys[r] : sample_key_mixed((unsigned)r, s_lo, mix);
         return (k & 0x7fffffffu) | 0x80000000u;
     }
     __device__ __forceinline__ unsigned key(int64_t r) const { return labels[r] == want ? of((int)r) : 0u; }
@@ -287,9 +264,9 @@ __global__ __launch_bounds__(RL_PART_THREADS) void rl_part_kernel(RlPlan pl, con
     const int r0 = part * RL_SELECT_SHARE;
     if (q.k <= 0 || part >= parts || r0 >= pl.R) return;                   // workgroup-uniform
     const int64_t row = (int64_t)n * pl.R;
-    const RlPartKeys src{RlKeys{labels + row, keys ? keys + row : nullptr, q.want, s_lo, (unsigned)n * 0x9e3779b9u + s_hi}, r0};
+    const RlPartKeys src{RlKeys{labels + row, keys ? keys + row : nullptr, q.want, s_lo, sample_mix((unsigned)n, s_hi)}, r0};
     int32_t* out = surv + (((int64_t)n * 2 + cls) * parts + part) * B;
-    const int c = select_in_order(src, (int64_t)min(RL_SELECT_SHARE, pl.R - r0), q.k, out, hist, wtot);
+    const int c = select_in_order(src, (int64_t)min(RL_SELECT_SHARE, pl.R - r0), q.k, hist, wtot, SelectStoreIndex{out});
     for (int j = tid; j < q.k; j += RL_PART_THREADS) out[j] = j < c ? out[j] + r0 : -1;
 }
 
@@ -307,10 +284,10 @@ __global__ __launch_bounds__(RL_SELECT_THREADS) void rl_select_kernel(RlPlan pl,
     const RlQuota q = rl_quota(counters, n, cls, pl.R, B, pos_cap);
     const int64_t row = (int64_t)n * pl.R;
     if (q.k > 0) {                                                        // workgroup-uniform
-        const RlKeys keys_of{labels + row, keys ? keys + row : nullptr, q.want, s_lo, (unsigned)n * 0x9e3779b9u + s_hi};
+        const RlKeys keys_of{labels + row, keys ? keys + row : nullptr, q.want, s_lo, sample_mix((unsigned)n, s_hi)};
         const RlSurvivorKeys from{keys_of, surv + ((int64_t)n * 2 + cls) * parts * B, q.k, B, pl.R};
-        const int c = parts <= 1 ? select_in_order(keys_of, (int64_t)pl.R, q.k, picked, hist, wtot)
-                                 : select_in_order(from, (int64_t)parts * q.k, q.k, picked, hist, wtot);
+        const int c = parts <= 1 ? select_in_order(keys_of, (int64_t)pl.R, q.k, hist, wtot, SelectStoreIndex{picked})
+                                 : select_in_order(from, (int64_t)parts * q.k, q.k, hist, wtot, SelectStoreIndex{picked});
         for (int j = tid; j < min(c, q.k); j += RL_SELECT_THREADS) {
             int r = parts <= 1 ? picked[j] : from.anchor(picked[j]);
             if (r < 0 || r >= pl.R) r = 0;                                // never: the indices are this call's own
@@ -419,7 +396,7 @@ __global__ __launch_bounds__(RL_THREADS) void rl_finish_kernel(const Partial* __
 int rl_plan(const int64_t* levels, int per, int n_levels, int64_t N, int A, double offset, RlPlan& pl) {
     UMR_CHECK_ARG(levels && n_levels >= 1 && n_levels <= RL_MAX_LEVELS, "rpn_loss: between 1 and 8 levels");
     UMR_CHECK_ARG(N >= 1 && N <= 65535, "rpn_loss: between 1 and 65535 images");
-    UMR_CHECK_ARG(A >= 1 && A <= RL_MAX_A, "rpn_loss: between 1 and 16 anchors per position");
+    UMR_CHECK_ARG(A >= 1 && A <= GRID_MAX_A, "rpn_loss: between 1 and 16 anchors per position");
     UMR_CHECK_ARG(offset >= 0.0 && offset < 1.0, "rpn_loss: offset must lie in [0, 1)");
     pl = RlPlan{};
     pl.L = n_levels; pl.N = (int)N; pl.A = A;

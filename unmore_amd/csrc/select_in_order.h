@@ -1,17 +1,20 @@
-// The k largest keys of a sequence, equal keys in sequence order, written in sequence order: the four-pass radix select of rpn.hip's
-// rpn_select, templated on where the keys come from.  Used by rpn_loss.hip only; rpn.hip keeps its own copy for now.
+// The k largest keys of a sequence, equal keys in sequence order, handed out in sequence order: a four-pass radix select over 8-bit
+// digits, templated on where the keys come from and on what is done with a selected entry.  Used by rpn.hip (per-level top-k of the
+// scores), rpn_loss.hip (the anchor batch) and roi_sample.hip (the proposal batch).
 //
-// Src gives `unsigned key(int64_t i) const`.  A key of 0 marks an entry that takes no part: it is never counted and never written, so
-// a caller selects among a subset of the sequence by giving the others 0 and its own entries keys >= 1.  k >= 1; when fewer than k
-// entries have a non-zero key, all of them are selected.
+// Src gives `unsigned key(Index i) const`, Index the integer type of the length n (int or int64_t): the loops count in it.  A key of
+// 0 marks an entry that takes no part: it is never counted and never handed out, so a caller selects among a subset of the sequence
+// by giving the others 0 and its own entries keys >= 1.  k >= 1; when fewer than k entries have a non-zero key, all of them are
+// selected.
 #pragma once
 #include "umr_common.h"
 
 // Every thread of the workgroup calls it (blockDim.x a multiple of 64, at most 1024); hist: 256 ints, wtot: 2 * 16 ints of LDS.
-// out_idx[j], j < the returned count (min(k, entries with a non-zero key), the same in every thread): the sequence index of the j-th
-// selected entry, ascending.  out_idx may be LDS or memory; it is complete after the call's final barrier.
-template <typename Src>
-__device__ int select_in_order(const Src& src, int64_t n, int k, int32_t* out_idx, int* hist, int* wtot) {
+// emit(j, i, key) is called once, by the thread that holds it, for the j-th selected entry in ascending sequence index i, j < the
+// returned count (min(k, entries with a non-zero key), the same in every thread).  What emit stores, in LDS or memory, is complete
+// after the call's final barrier.
+template <typename Src, typename Index, typename Emit>
+__device__ int select_in_order(const Src& src, Index n, int k, int* hist, int* wtot, Emit emit) {
     const int tid = threadIdx.x, T = blockDim.x, lane = tid & 63, wv = tid >> 6, nw = T >> 6;
     unsigned prefix = 0u, mask = 0u;
     int remaining = k;
@@ -19,7 +22,7 @@ __device__ int select_in_order(const Src& src, int64_t n, int k, int32_t* out_id
         __syncthreads();
         for (int b = tid; b < 256; b += T) hist[b] = 0;
         __syncthreads();
-        for (int64_t i = tid; i < n; i += T) {
+        for (Index i = tid; i < n; i += T) {
             const unsigned key = src.key(i);
             if (key && (key & mask) == prefix) atomicAdd(&hist[(key >> shift) & 255u], 1);
         }
@@ -41,11 +44,12 @@ __device__ int select_in_order(const Src& src, int64_t n, int k, int32_t* out_id
     }
     // prefix: the k-th largest key; `remaining` >= 1 of the keys equal to it are taken, the first ones (or prefix 0 and none: all)
     int n_gt = 0, n_eq = 0, par = 0;
-    for (int64_t base = 0; base < n; base += T) {
-        const int64_t i = base + tid;
+    for (Index base = 0; base < n; base += T) {
+        const Index i = base + tid;
+        unsigned key = 0u;
         bool gt = false, eq = false;
         if (i < n) {
-            const unsigned key = src.key(i);
+            key = src.key(i);
             gt = key > prefix;
             eq = key == prefix && key != 0u;
         }
@@ -62,7 +66,7 @@ __device__ int select_in_order(const Src& src, int64_t n, int k, int32_t* out_id
         }
         if (gt || (eq && e < remaining)) {
             const int at = g + min(e, remaining);
-            if (at >= 0 && at < k) out_idx[at] = (int32_t)i;        // always
+            if (at >= 0 && at < k) emit(at, i, key);                // always
         }
         n_gt += tg;
         n_eq += te;
@@ -71,3 +75,9 @@ __device__ int select_in_order(const Src& src, int64_t n, int k, int32_t* out_id
     __syncthreads();
     return n_gt + min(n_eq, remaining);
 }
+
+// the emit that keeps the sequence index alone: out[j] = i
+struct SelectStoreIndex {
+    int32_t* out;
+    __device__ __forceinline__ void operator()(int j, int64_t i, unsigned) const { out[j] = (int32_t)i; }
+};
