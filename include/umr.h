@@ -939,6 +939,32 @@ int umr_roi_sample(const int64_t* table, int n_images, int64_t n_cand, int64_t n
                    int64_t* out_classes, float* out_gt_boxes, float* out_gt_scores, int64_t* out_matched_idxs, int32_t* out_sampled_idxs,
                    int32_t* counts, int32_t* counters, void* workspace, int64_t workspace_bytes, umr_stream_t stream);
 
+/* ---- the detector's input path (cad/data/dataset_mapper.py:152-213 with ResizeShortestEdge + RandomFlip, cad/data/transforms/
+ * transform.py:94-163, GeneralizedRCNN.preprocess_image, cad/modeling/meta_arch/rcnn.py:229-240; csrc/det_input.hip) ----------------------
+ * Three entries, each ONE launch for a whole ragged batch of B images.  desc: int64 [B][fields] ON THE DEVICE (addresses as integers);
+ * tab: int32 [tab_len] on the device, the tables the descriptors point into by element offset.  The host builds the tables in float64
+ * (unmore_amd/detector_input.py); the device side is integer only, so the bytes are PIL's.
+ * det_resize_bilinear  PIL Image.resize(BILINEAR) on 8-bit RGB, HWC in, planar CHW out, flip at the store.  desc [B][16]: src u8 [H,W,3],
+ *   dst u8 [3,nh,nw], H, W, nh, nw, flip (1 horizontal, 2 vertical), then per axis (horizontal: 7-9, vertical: 10-12) the offset of
+ *   its (lo, n) pairs [out][2], of its weights [out][ksize] (22 fractional bits) and ksize; TH, TW (output tile, TW <= 64, the input rows
+ *   a tile reads times TW <= 10880) and the image's first tile; total_tiles = the grid.  byte = clip((2^21 + sum_j in[lo + j] * k_j) >>
+ *   22), horizontal pass first, its bytes staged in LDS.  An axis that keeps its size: lo = i, n = 1, k = 2^22.
+ * det_resize_nearest   PIL Image.resize(NEAREST) of N masks per image, any non-zero input byte = set, 0 / 1 bytes out.  desc [B][13]:
+ *   src (mask n at src + n * stride), dst u8 [N,nh,nw], N, H, W, nh, nw, flip, the offsets of the column table [nw] and the row table
+ *   [nh] (source indices), the image's first flag, its first workgroup (a workgroup owns ceil(4096 / nw) rows, rounded up to a
+ *   multiple of 4, of one mask;
+ *   total_blocks = the grid), stride.  flags int32 [n_flags], ZEROED by the caller: flag |= 1 iff the resized mask has a set pixel (one
+ *   integer atomic OR per workgroup).
+ * det_normalize_pad    out float32 [B,3,Hp,Wp], 16-byte aligned: (float32(u8) - mean[c]) / std[c] (IEEE divide) at the top left, pad_value
+ *   elsewhere; every element is written.  desc [B][4]: src u8 [3,h,w], h, w, 0.
+ * A descriptor that breaks its own bounds (sizes, table slices past tab_len, flags past n_flags, a tile that does not fit) is skipped;
+ * an index read from a table is checked before it is used.  No synchronisation, nothing allocated; the same input, the same bytes. */
+int umr_det_resize_bilinear(const int64_t* desc, int B, const int32_t* tab, int64_t tab_len, int64_t total_tiles, umr_stream_t stream);
+int umr_det_resize_nearest(const int64_t* desc, int B, const int32_t* tab, int64_t tab_len, int64_t total_blocks, int32_t* flags,
+                           int64_t n_flags, umr_stream_t stream);
+int umr_det_normalize_pad(const int64_t* desc, int B, int Hp, int Wp, float mean0, float mean1, float mean2, float std0, float std1,
+                          float std2, float pad_value, float* out, umr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
