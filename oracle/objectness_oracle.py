@@ -536,17 +536,18 @@ def nms(boxes, scores, iou_threshold):
     order = np.argsort(-np.asarray(scores, dtype=np.float64), kind="stable")
     keep, removed = [], np.zeros(len(b), dtype=bool)
     area = (b[:, 2] - b[:, 0]) * (b[:, 3] - b[:, 1])
+    lo = lambda x, y: np.where(y < x, y, x)                 # std::min(x, y) and std::max(x, y), also for a NaN
+    hi = lambda x, y: np.where(y > x, y, x)
+    zero, thr = np.float32(0), np.float32(iou_threshold)
     for r, i in enumerate(order):
         if removed[r]:
             continue
         keep.append(int(i))
-        for r2 in range(r + 1, len(order)):
-            j = order[r2]
-            w = np.float32(max(np.float32(min(b[i, 2], b[j, 2]) - max(b[i, 0], b[j, 0])), np.float32(0)))
-            h = np.float32(max(np.float32(min(b[i, 3], b[j, 3]) - max(b[i, 1], b[j, 1])), np.float32(0)))
-            inter = np.float32(w * h)
-            with np.errstate(divide="ignore", invalid="ignore"):
-                iou = np.float32(inter / np.float32(np.float32(area[i] + area[j]) - inter))
-            if iou > np.float32(iou_threshold):
-                removed[r2] = True
+        c = b[order[r + 1:]]                                # the later ranks at once: float32 arrays, one rounding per operation
+        with np.errstate(divide="ignore", invalid="ignore"):
+            w = hi(lo(b[i, 2], c[:, 2]) - hi(b[i, 0], c[:, 0]), zero)
+            h = hi(lo(b[i, 3], c[:, 3]) - hi(b[i, 1], c[:, 1]), zero)
+            inter = w * h
+            iou = inter / ((area[i] + area[order[r + 1:]]) - inter)
+            removed[r + 1:] |= iou > thr
     return np.asarray(keep, dtype=np.int64)

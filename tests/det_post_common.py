@@ -258,3 +258,37 @@ def selection_batch(seed, K, class_specific, rows=(0, 1, 63, 65, 300, 1100)):
 
 def load_fixture():
     return np.load(os.path.join(HERE, "golden", "det_post.npz"), allow_pickle=False)
+
+
+def ranked_image(boxes):
+    """one image of one class whose candidates are `boxes` in this order: score 1 - r / 1024 for row r (exact, above 0.05 for r < 972)"""
+    boxes = np.asarray(boxes, F32).reshape(-1, 4)
+    n = len(boxes)
+    assert n < 972
+    scores = np.zeros((n, 2), F32)
+    scores[:, 0] = F32(1) - np.arange(n, dtype=F32) / F32(1024)
+    return boxes, scores, (64, 65536)
+
+
+# the class predicate: (rows, classes) kept of class_pairs' two images, in output order
+CLASS_PAIRS_KEPT = ([(0, 0), (0, 1)], [(0, 0)])
+
+
+def class_pairs(class_specific):
+    """two images of K = 2 classes.  The first: one row that passes under both classes with the same box -- two candidates that overlap
+    fully and differ in class, both kept.  The second: two rows with that box under class 0 alone -- one kept."""
+    box = np.array([10, 10, 50, 40], F32)
+    reps = 2 if class_specific else 1
+    one = (np.tile(box, (1, reps)), np.array([[0.9, 0.8, 0.0]], F32), (64, 64))
+    two = (np.tile(box, (2, reps)), np.array([[0.9, 0.01, 0.0], [0.8, 0.02, 0.0]], F32), (64, 64))
+    return [one, two]
+
+
+def many_candidates(R, K, seed=7):
+    """one image whose R x K (row, class) pairs all pass 0.05: boxes 20 to 60 px per side around centres in a 200 x 200 frame, so that a greedy NMS at
+    0.5 keeps several hundred per class; class-agnostic boxes [R, 4], scores [R, K + 1]"""
+    rng = np.random.RandomState(seed + R + K)
+    c, wh = rng.uniform(0, 200, (R, 2)), rng.uniform(20, 60, (R, 2))
+    boxes = np.concatenate([c - wh / 2, c + wh / 2], axis=1).astype(F32)
+    scores = np.concatenate([rng.uniform(0.06, 1, (R, K)), np.zeros((R, 1))], axis=1).astype(F32)
+    return boxes, scores, (240, 240)

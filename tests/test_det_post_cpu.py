@@ -249,3 +249,22 @@ def test_argument_errors_and_no_cpu_fallback():
             call()
     with pytest.raises(ValueError, match="same device"):
         D.fast_rcnn_inference([b], [s.to("meta")], [(10, 10)], 0.0, 0.5, 100)
+
+
+def test_selection_restatement_on_the_constructed_blocks():
+    """tests/nms_cases.py through select_numpy: the chains keep [A, C], 64 duplicates leave one, two zero-area boxes stay; a top-k cut is
+    a prefix; the same box is kept once per class"""
+    import nms_cases as NC
+    boxes, kept = NC.constructed_boxes()
+    b, s, shape = C.ranked_image(boxes)
+    rows = C.select_numpy(b, s, shape, 0.05, NC.THRESH, -1)[3]
+    NC.check_expected(rows)
+    assert C.select_numpy(b, s, shape, 0.05, NC.THRESH, 65)[3].tolist() == kept[:65]
+    ch = list(NC.CHAIN_IN_ONE_BLOCK)
+    assert C.select_numpy(*C.ranked_image(boxes[ch]), 0.05, NC.THRESH, -1)[3].tolist() == [0, 2]
+    assert C.select_numpy(*C.ranked_image(boxes[list(NC.DUPLICATES)]), 0.05, NC.THRESH, -1)[3].tolist() == [0]
+    assert C.select_numpy(*C.ranked_image(boxes[list(NC.ZERO_AREA)]), 0.05, NC.THRESH, -1)[3].tolist() == [0, 1]
+    for specific in (False, True):
+        for (b, s, shape), want in zip(C.class_pairs(specific), C.CLASS_PAIRS_KEPT):
+            got = C.select_numpy(b, s, shape, 0.05, NC.THRESH, -1)
+            assert list(zip(got[3].tolist(), got[2].tolist())) == want

@@ -101,6 +101,67 @@ def test_selection_fixture_on_the_device():
         assert items[k]["scores"].cpu().numpy().tobytes() == fx[f"im{k}_pred_scores"].tobytes()
 
 
+# ---------------------------------------------------------------------------------------------------------------- the shared scan
+def _same(got, want, n=None):
+    """a device result (boxes, scores, classes, rows) equals the first n entries of a restatement's or of another device result"""
+    n = len(want[0]) if n is None else n
+    return (len(got[0]) == n and np.array_equal(got[3], want[3][:n]) and np.array_equal(got[2], want[2][:n]) and
+            got[0].tobytes() == want[0][:n].tobytes() and got[1].tobytes() == want[1][:n].tobytes())
+
+
+@pytest.mark.parametrize("R,K", [(4097, 1), (4096, 2)])
+def test_selection_with_two_removed_words_per_lane(R, K):
+    """4097 candidates, the first count that needs the second word of removed set per lane, and 8192, the table's maximum; several
+    hundred survive per class, past rank 4096 too; the cut at 100 is a prefix"""
+    dev = _dev()
+    batch = [C.many_candidates(R, K)]
+    want = C.select_numpy(*batch[0], ST, NT, -1)
+    print("kept", len(want[0]), "of", R * K)
+    assert R * K > 4096 and 300 < len(want[0]) < R * K // 2
+    assert _same(_run_select(batch, -1, dev)[0], want)
+    assert _same(_run_select(batch, 100, dev)[0], want, 100)
+
+
+def test_selection_on_the_constructed_blocks():
+    """tests/nms_cases.py: chains inside a 64-rank block, into the next and over a wholly suppressed one, a block of duplicates, two
+    zero-area boxes; test_det_post_cpu.py checks that the restatement gives the constructed list"""
+    import nms_cases as NC
+    dev = _dev()
+    batch = [C.ranked_image(NC.constructed_boxes()[0])]
+    got = _run_select(batch, -1, dev)[0]
+    assert _same(got, C.select_numpy(*batch[0], ST, NC.THRESH, -1))
+    NC.check_expected(got[3])
+
+
+@pytest.fixture(scope="module")
+def limited():
+    """the constructed image (193 kept of 322) and one of 30 separate boxes, whose cap min(P, topk) = 30 is below every topk from 63 on"""
+    import nms_cases as NC
+    dev = _dev()
+    batch = [C.ranked_image(NC.constructed_boxes()[0]), C.ranked_image(NC.line_boxes(128 * np.arange(30)))]
+    return {topk: _run_select(batch, topk, dev) for topk in (-1, 0, 1, 63, 64, 65, 128)}
+
+
+@pytest.mark.parametrize("topk", [0, 1, 63, 64, 65, 128])
+def test_selection_limit_is_a_prefix(limited, topk):
+    """63 ranks are kept in the first block of 64: a limit of 63 ends the walk there, 64 and 65 end it inside the second block"""
+    full = limited[-1]
+    assert len(full[0][0]) > 130 and len(full[1][0]) == 30
+    assert _same(limited[topk][0], full[0], topk)                              # counts == topk
+    assert _same(limited[topk][1], full[1], min(topk, 30))                     # cap < topk
+
+
+@pytest.mark.parametrize("specific", [False, True])
+def test_selection_class_predicate(specific):
+    """the same box under two classes is kept twice, under one class once"""
+    dev = _dev()
+    batch = C.class_pairs(specific)
+    got = _run_select(batch, -1, dev)
+    for g, (b, s, sh), kept in zip(got, batch, C.CLASS_PAIRS_KEPT):
+        assert _same(g, C.select_numpy(b, s, sh, ST, NT, -1))
+        assert list(zip(g[3].tolist(), g[2].tolist())) == kept
+
+
 # ---------------------------------------------------------------------------------------------------------------- the paste
 PASTE_CASES = ((28, 1, 96, 130, False), (7, 3, 37, 53, False), (28, 3, 37, 53, True), (7, 1, 96, 130, False))
 

@@ -41,3 +41,19 @@ def test_oracle_nms_known_answers():
     assert orc.nms(b, np.array([0.1, 0.9, 0.2, 0.3, 0.8]), 0.5).tolist() == [1, 4]
     assert orc.nms(b, np.ones(5), 0.7).tolist() == [0, 1, 2, 4]          # IoU 0.68 and 0.64 pass a 0.7 threshold, the duplicate does not
     assert orc.nms(b[:1], np.ones(1), 0.5).tolist() == [0]
+
+
+def test_oracle_nms_on_the_constructed_blocks():
+    """tests/nms_cases.py: the chains keep [A, C] inside a block, into the next and over a wholly suppressed one; 64 duplicates leave one;
+    the two zero-area boxes stay -- so that the device test on the same boxes cannot pass vacuously"""
+    import nms_cases as NC
+    from oracle import objectness_oracle as orc
+    boxes, kept = NC.constructed_boxes()
+    n = len(boxes)
+    NC.check_expected(orc.nms(boxes, np.arange(n, 0, -1), NC.THRESH))
+    back = orc.nms(boxes[::-1], np.arange(1, n + 1), NC.THRESH)                # the same ranks from the reversed input order
+    assert (n - 1 - back).tolist() == kept
+    a, b, c = NC.CHAIN_IN_ONE_BLOCK
+    assert orc.nms(boxes[[a, b, c]], np.ones(3), NC.THRESH).tolist() == [0, 2] and orc.nms(boxes[[b, c]], np.ones(2), NC.THRESH).tolist() == [0]
+    assert orc.nms(boxes[list(NC.DUPLICATES)], np.ones(64), NC.THRESH).tolist() == [0]
+    assert orc.nms(boxes[list(NC.ZERO_AREA)], np.ones(2), NC.THRESH).tolist() == [0, 1]

@@ -152,7 +152,7 @@ def test_discover_image_end_to_end_and_nms():
     assert list(out) == [7] and np.array_equal(out[7], boxes.cpu().numpy())
 
 
-@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 300, 1500])
+@pytest.mark.parametrize("n", [1, 2, 63, 64, 65, 128, 129, 300, 1500, 4095, 4096])
 def test_nms_kernel_equals_the_oracle(n):
     from oracle import objectness_oracle as orc
     from unmore_amd import reasoning
@@ -169,6 +169,24 @@ def test_nms_kernel_equals_the_oracle(n):
             ref = orc.nms(b, scores, thr)
             assert got.dtype == torch.int64 and got.cpu().numpy().tolist() == ref.tolist(), (n, thr)
     assert reasoning.nms(torch.zeros((0, 4), device=DEV), torch.zeros(0, device=DEV), 0.5).numel() == 0
+
+
+def test_nms_kernel_limit_and_constructed_blocks():
+    """4097 boxes are refused (one word of removed set per lane); tests/nms_cases.py: chains inside a 64-rank block, into the next and
+    over a wholly suppressed one, a block of duplicates, two zero-area boxes -- the oracle's list, which test_object_discovery_cpu.py
+    checks to be the constructed one"""
+    import nms_cases as NC
+    from oracle import objectness_oracle as orc
+    from unmore_amd import reasoning
+    with pytest.raises(RuntimeError, match="at most 4096 boxes"):
+        reasoning.nms(torch.zeros((4097, 4), device=DEV), torch.zeros(4097, device=DEV), 0.5)
+    boxes, kept = NC.constructed_boxes()
+    n = len(boxes)
+    for b, scores in ((boxes, np.arange(n, 0, -1)), (boxes[::-1].copy(), np.arange(1, n + 1))):     # rank = index, and rank = n - 1 - index
+        scores = scores.astype(np.float32)
+        got = reasoning.nms(torch.from_numpy(b).to(DEV), torch.from_numpy(scores).to(DEV), NC.THRESH).cpu().numpy()
+        assert got.tolist() == orc.nms(b, scores, NC.THRESH).tolist()
+        NC.check_expected(got if scores[0] > scores[1] else n - 1 - got)
 
 
 @pytest.mark.parametrize("backbone,dtype_name", [("dpt_tiny", "float32"), ("dpt_base", "float32"), ("dpt_base", "bfloat16")])

@@ -323,3 +323,16 @@ def test_grid_anchor_and_cell_value_errors():
         rpn.cell_anchors([[32], [64]], [[1.0], [1.0], [1.0]])
     with pytest.raises(ValueError, match="rpn: sizes is a sequence"):
         rpn.cell_anchors([32], [1.0])
+
+
+def test_nms_restatement_on_the_constructed_blocks():
+    """tests/nms_cases.py through nms_np: the chains keep [A, C], 64 duplicates leave one, two zero-area boxes stay (with flag 0: the
+    device flags an empty box and never keeps it); a flagged rank suppresses nothing"""
+    import nms_cases as NC
+    boxes, kept = NC.constructed_boxes()
+    NC.check_expected(C.nms_np(boxes, np.zeros(len(boxes), np.uint8), NC.THRESH))
+    a, b, c = NC.CHAIN_IN_ONE_BLOCK
+    assert C.nms_np(boxes[[a, b, c]], [0, 0, 0], NC.THRESH).tolist() == [0, 2] and C.nms_np(boxes[[b, c]], [0, 0], NC.THRESH).tolist() == [0]
+    assert C.nms_np(boxes[[b, c]], [2, 0], NC.THRESH).tolist() == [1]
+    assert C.nms_np(boxes[list(NC.DUPLICATES)], np.zeros(64), NC.THRESH).tolist() == [0]
+    assert C.nms_np(boxes[list(NC.ZERO_AREA)], [0, 0], NC.THRESH).tolist() == [0, 1]

@@ -265,6 +265,52 @@ def test_nms_candidate_counts(hw):
     assert counters[0, 0, 0] == n_cand and counters[0, 0, 3] > 0.2 * n_cand and counters[0, 0, 4] == len(got[0][1]) > 0
 
 
+def _line_level(q, lowered=()):
+    """One level (N = 1, A = 1, H = 1, W = len(q), stride 4, a 64 x 64 cell anchor) whose candidate of rank r decodes exactly to the box
+    (q[r], 0, q[r] + 64, 32) of tests/nms_cases.py: logit len(q) - x makes position x rank x; dw = dh = 0 and dx = (q + 32 - 4 x) / 64, a
+    multiple of 1/64, keep every operation of the decode exact; the frame (64, 65536) clips y1 = -32 to 0 and nothing else.  The ranks in
+    `lowered` get dy = -12 / 64: rows -44 .. 20, 20 high after the clip."""
+    K = len(q)
+    logits = [np.arange(K, 0, -1, dtype=F32).reshape(1, 1, 1, K)]
+    d = np.zeros((1, 4, 1, K), F32)
+    d[0, 0, 0] = (np.asarray(q, np.float64) + 32 - 4 * np.arange(K)) / 64
+    d[0, 1, 0, list(lowered)] = -12 / 64
+    return logits, [d], [C.cell_anchors_np((64,), (1.0,))], (4,), [(64, 65536)]
+
+
+def test_nms_on_the_constructed_blocks():
+    """tests/nms_cases.py as one level's candidates: chains inside a 64-rank block, into the next and over a wholly suppressed one, and a
+    block of duplicates.  The zero-area pair is left out: a box of no width is flagged empty here and never reaches the scan as valid."""
+    import nms_cases as NC
+    q, width, kept = NC.constructed(zero_area=False)
+    logits, deltas, cells, strides, sizes = _line_level(q)
+    kw = {"nms_thresh": NC.THRESH, "pre_nms_topk": 4096, "post_nms_topk": 4096}
+    got, cand, counters = _run(logits, deltas, cells, strides, sizes, **kw)
+    _check_layers(got, cand, counters, logits, deltas, cells, strides, sizes, NC.THRESH, 4096, 4096)
+    assert np.array_equal(_bits(cand["boxes"][0]), _bits(NC.line_boxes(q)))               # the decode is exact
+    assert np.array_equal(_bits(got[0][0]), _bits(NC.line_boxes(q)[kept]))
+    assert counters[0, 0].tolist() == [len(q), 0, 0, len(q) - len(kept), len(kept)]
+
+
+def test_nms_starts_from_the_valid_set():
+    """K = 65, the last valid word holds one rank.  Rank 30 is flagged empty (20 high, min_box_size 24) and lies on rank 50 with IoU
+    20 / 32: its row of the matrix has rank 50's bit, and rank 50 is kept because an invalid rank suppresses nothing.  Ranks 62, 63, 64
+    are a chain over the word boundary: 63 goes, 64 -- the partial word's only rank -- stays."""
+    import nms_cases as NC
+    q = 1000 + 128 * np.arange(65)
+    q[30] = q[50] = 0
+    q[62], q[63], q[64] = 200, 216, 232
+    logits, deltas, cells, strides, sizes = _line_level(q, lowered=(30,))
+    kw = {"nms_thresh": NC.THRESH, "pre_nms_topk": 4096, "post_nms_topk": 4096, "min_box_size": 24.0}
+    got, cand, counters = _run(logits, deltas, cells, strides, sizes, **kw)
+    _check_layers(got, cand, counters, logits, deltas, cells, strides, sizes, NC.THRESH, 4096, 4096, min_box=24.0)
+    assert cand["flags"][0].tolist() == [2 if r == 30 else 0 for r in range(65)]
+    assert cand["boxes"][0, 30].tolist() == [0, 0, 64, 20] and C.iou_row(cand["boxes"][0, 30], cand["boxes"][0, 50])[0] > NC.THRESH
+    kept = [r for r in range(65) if r not in (30, 63)]
+    assert np.array_equal(_bits(got[0][0]), _bits(NC.line_boxes(q)[kept]))
+    assert counters[0, 0].tolist() == [65, 0, 1, 1, 63]
+
+
 def test_an_image_without_a_box_left():
     """every dx of the second image is 40 anchor widths to the right: all of its boxes clip to zero width, its count is 0 and its views
     are empty"""

@@ -1,5 +1,5 @@
 // The box geometry, the grid anchors and the sampling hash that the detector's kernels share (box_loss.hip, rpn.hip,
-// rpn_loss.hip, roi_sample.hip, det_post.hip).  These functions carry the bit-exactness contract with Detectron2 and torchvision: which
+// rpn_loss.hip, roi_sample.hip, det_post.hip, nms.hip).  These functions carry the bit-exactness contract with Detectron2 and torchvision: which
 // IoU form hands a NaN on, the correctly rounded divisions, the float32 value of log(1000 / 16), the hash that draws the
 // samples.  Each is written once, here.
 //
@@ -37,7 +37,8 @@ __device__ __forceinline__ float box_iou_match(float ax1, float ay1, float ax2, 
     return inter > 0.f ? __fdiv_rn(inter, (a_area + b_area) - inter) : 0.f;
 }
 
-// The suppression's form (torchvision's nms kernel, which both NMS steps follow): std::max / std::min written as fmaxf / fminf,
+// The suppression's form (torchvision's nms kernel; called from nms_bitmask.h alone, which every NMS here runs on): std::max / std::min
+// written as fmaxf / fminf,
 //   w = max(0, min(a.x2, b.x2) - max(a.x1, b.x1)), h likewise, inter = w * h, iou = inter / ((area_a + area_b) - inter),
 // correctly rounded and with no test of inter: two empty boxes give 0 / 0 = NaN, and `iou > nms_thresh` is then false (not suppressed).
 __device__ __forceinline__ float box_iou_nms(const f32x4 a, float a_area, const f32x4 b) {

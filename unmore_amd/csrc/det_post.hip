@@ -11,16 +11,13 @@
 //                         8192).  Then every candidate counts its rank, #{j : s_j > s_i or (s_j == s_i and j < i)} -- descending score,
 //                         equal scores in candidate order, a permutation because no NaN score is a candidate -- and writes its clipped
 //                         box, score and p to that slot of the workspace.
-//   dp_mask_kernel        one wave per (64 ranks i, 64 ranks j) tile of an image's upper triangle: bit j of word (i, j / 64) = j > i, same
-//                         class, IoU(i, j) > nms_thresh.
-//   dp_scan_kernel        one wave per image walks the ranks in order; lane l holds words l and l + 64 of the removed set; a rank that is
-//                         not removed is kept and ORs its row into the set; stops at topk.  The kept ranks go through LDS and are written
-//                         by the whole wave: boxes, scores, classes, rows, and the count.
-// Arithmetic, float32, no contraction, every operation rounded on its own (det_box.h: box_clip, box_area, box_iou_nms):
+//   dp_mask_kernel        one wave per 64 x 64 tile of an image's upper triangle: the suppression matrix of nms_bitmask.h with the
+//                         predicate "same class".
+//   dp_scan_kernel        one wave per image: nms_bitmask.h's greedy scan over all ranks, two words per lane (<= 8192), limited to
+//                         min(topk, cap).  The kept ranks go through LDS and are written by the whole wave: boxes, scores, classes,
+//                         rows, and the count.
+// Arithmetic, float32, no contraction, every operation rounded on its own (det_box.h: box_clip; the suppression: nms_bitmask.h):
 //   clip        x < 0 ? 0 : (x > width ? width : x)          (a NaN stays a NaN; none arrives here)
-//   area        (x2 - x1) * (y2 - y1)
-//   iou(a, b)   w = max(0, min(a.x2, b.x2) - max(a.x1, b.x1)), h likewise, inter = w * h,
-//               iou = inter / ((area_a + area_b) - inter), correctly rounded; suppressed iff iou > nms_thresh (0 / 0 = NaN: not suppressed)
 //
 // The paste (Detectron2's _do_paste_mask: F.grid_sample(align_corners=False, zero padding) of the M x M probabilities, then >= threshold):
 // one workgroup of 256 threads per mask; prob = 1 / (1 + expf(-logit)) once into LDS as float32 (bfloat16 logits are widened first).
@@ -37,6 +34,7 @@
 #pragma clang fp contract(off)
 #include "umr_common.h"
 #include "det_box.h"
+#include "nms_bitmask.h"
 #include "rle_stream.h"
 #include <algorithm>
 #include <float.h>
@@ -154,15 +152,9 @@ __global__ __launch_bounds__(64) void dp_mask_kernel(const umr_dp_image* __restr
     __syncthreads();
     const int i = rb * 64 + t;
     if (i >= n) return;
-    const f32x4 a = ws.sbox[cf + i];
     const int cls = ws.spair[cf + i] % sh.K;
-    const float a_area = box_area(a[0], a[1], a[2], a[3]);
-    unsigned long long bits = 0ull;
-    for (int jj = 0; jj < nj; ++jj) {
-        const float iou = box_iou_nms(a, a_area, cbox[jj]);
-        if (j0 + jj > i && ccls[jj] == cls && iou > nms_thresh) bits |= 1ull << jj;
-    }
-    ws.mat[im.mat_first + (int64_t)i * words + cb] = bits;
+    ws.mat[im.mat_first + (int64_t)i * words + cb] =
+        nms_tile_word(ws.sbox[cf + i], i, cbox, j0, nj, nms_thresh, [&](int jj) { return ccls[jj] == cls; });
 }
 
 __global__ __launch_bounds__(64) void dp_scan_kernel(const umr_dp_image* __restrict__ images, DpShape sh, int topk, DpWork ws,
@@ -180,19 +172,9 @@ __global__ __launch_bounds__(64) void dp_scan_kernel(const umr_dp_image* __restr
     const int n = min(ws.n_cand[k], P), nw = dp_words(n);
     const int limit = topk >= 0 ? min(topk, im.cap) : im.cap;
     const unsigned long long* mat = ws.mat + im.mat_first;
-    unsigned long long rem0 = 0ull, rem1 = 0ull;                    // words lane and lane + 64 of the removed set
-    int kept = 0;
-    for (int i = 0; i < n && kept < limit; ++i) {                   // wave-uniform
-        const int w = i >> 6;
-        const unsigned long long v0 = __shfl(rem0, w & 63), v1 = __shfl(rem1, w & 63);
-        const unsigned long long wi = w < 64 ? v0 : v1;
-        if ((wi >> (i & 63)) & 1ull) continue;
-        if (lane == 0) kept_rank[kept] = i;
-        ++kept;
-        const unsigned long long* row = mat + (int64_t)i * words;  // the words [w, nw) of row i were written by dp_mask_kernel
-        if (lane >= w && lane < nw) rem0 |= row[lane];
-        if (lane + 64 >= w && lane + 64 < nw) rem1 |= row[lane + 64];
-    }
+    // the row pitch comes from P, the words that dp_mask_kernel wrote from n
+    const unsigned long long valid[2] = {nms_all_valid(lane, n), nms_all_valid(lane + 64, n)};
+    const int kept = nms_greedy_scan<2>(mat, words, nw, n, valid, limit, kept_rank);
     __syncthreads();
     if (lane == 0) counts[k] = kept;
     for (int j = lane; j < kept; j += 64) {

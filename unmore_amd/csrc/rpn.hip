@@ -12,20 +12,16 @@
 //   rpn_rank_kernel    one workgroup of 1024 threads per (level, image): the same select over the level's scores (one part) or over its
 //                      parts' survivors, K of them in f order into LDS; every one counts its rank #{j : key_j > key_i or (key_j == key_i
 //                      and j < i)} (a permutation), decodes its anchor and writes the clipped box, the logit, f and a flag to rank's slot.
-//   rpn_mask_kernel    one wave per (64 ranks i, 64 ranks j) tile of a level's upper triangle: bit j of word (i, j / 64) = j > i and
-//                      IoU(i, j) > nms_thresh (det_post.hip's dp_mask_kernel without classes).
-//   rpn_scan_kernel    one wave per (level, image) walks the valid ranks in order, 64 at a time; lane l holds word l of the removed set
-//                      (K <= 4096: one word per lane).  Inside a block of 64 ranks the greedy walk runs on the diagonal tile held in
-//                      registers (a rank that is valid and not removed is kept and removes its row's bits); then the kept rows are
-//                      ORed into the words after the block with their loads in flight together.  The kept boxes and logits are
-//                      written compacted, in rank order.
+//   rpn_mask_kernel    one wave per 64 x 64 tile of a level's upper triangle: the suppression matrix of nms_bitmask.h, no predicate.
+//   rpn_scan_kernel    one wave per (level, image): nms_bitmask.h's greedy scan from the level's valid set, one word per lane
+//                      (K <= 4096), no limit.  The kept boxes and logits are written compacted, in rank order.
 //   rpn_merge_kernel   a thread per kept candidate: its place in the image's order = its place in its level + the number of kept
 //                      candidates of every lower level with logit >= its own + of every higher level with logit > its own (bisection in
 //                      the levels' sorted lists); the first post_nms_topk are written.
 // Order of the scores: key(v) = 0xffffffff for a NaN; else with u = bits(v == 0 ? +0 : v): u < 0 ? ~u : u | 0x80000000.  Larger key =
 // larger value, a NaN above +inf, -0.0 == +0.0 (torch.topk's order); equal keys in ascending f = (y * W + x) * A + a.
-// Arithmetic, float32, no contraction, every operation rounded on its own (det_box.h: grid_anchor, box_apply_deltas, box_clip,
-// box_iou_nms):
+// Arithmetic, float32, no contraction, every operation rounded on its own (det_box.h: grid_anchor, box_apply_deltas, box_clip; the
+// suppression's IoU and its strict `>`: nms_bitmask.h):
 //   anchor      sx = float(x * stride) + off, sy = float(y * stride) + off  (off = offset * stride, exact);  (sx + c0, sy + c1, sx + c2, sy + c3)
 //               for the level's cell anchor c of index a
 //   apply       w = x2 - x1; cx = x1 + .5 w; dx = dx / wx; dw = min(dw / ww, log(1000 / 16)); pcx = dx * w + cx; pw = expf(dw) * w;
@@ -33,11 +29,10 @@
 //   non-finite  a decoded coordinate or the logit is NaN or +-inf: dropped and counted (flag 1)
 //   clip        x < 0 ? 0 : (x > width ? width : x)
 //   empty       not (x2 - x1 > min_box_size and y2 - y1 > min_box_size) after the clip: dropped and counted (flag 2)
-//   iou(a, b)   w = max(0, min(a.x2, b.x2) - max(a.x1, b.x1)), h likewise, inter = w * h,
-//               iou = inter / ((area_a + area_b) - inter), correctly rounded; suppressed iff iou > nms_thresh (0 / 0 = NaN: not suppressed)
 #pragma clang fp contract(off)
 #include "umr_common.h"
 #include "det_box.h"
+#include "nms_bitmask.h"
 #include "select_in_order.h"
 #include <algorithm>
 #include <float.h>
@@ -206,21 +201,8 @@ __global__ __launch_bounds__(64) void rpn_mask_kernel(RpnPlan pl, RpnWork ws, fl
     __syncthreads();
     const int i = rb * 64 + t;
     if (i >= K) return;
-    const f32x4 a = cbox[cb + i];
-    const float a_area = box_area(a[0], a[1], a[2], a[3]);
-    unsigned long long bits = 0ull;
-    for (int jj = 0; jj < nj; ++jj) {
-        const f32x4 b = tile[jj];
-        const float iou = box_iou_nms(a, a_area, b);
-        if (j0 + jj > i && iou > nms_thresh) bits |= 1ull << jj;
-    }
+    const unsigned long long bits = nms_tile_word(cbox[cb + i], i, tile, j0, nj, nms_thresh, NmsAlways{});
     ws.mat[(long long)n * pl.mat_total + lv.mat_first + (long long)i * words + cbk] = bits;
-}
-
-// lane `src` (wave-uniform) of a 64-bit value, through the scalar unit: no LDS round trip on the scan's serial chain
-__device__ __forceinline__ unsigned long long rpn_lane_value(unsigned long long v, int src) {
-    const unsigned lo = __builtin_amdgcn_readlane((int)(unsigned)v, src), hi = __builtin_amdgcn_readlane((int)(unsigned)(v >> 32), src);
-    return ((unsigned long long)hi << 32) | lo;
 }
 
 __global__ __launch_bounds__(64) void rpn_scan_kernel(RpnPlan pl, RpnWork ws, const f32x4* __restrict__ cbox,
@@ -230,42 +212,10 @@ __global__ __launch_bounds__(64) void rpn_scan_kernel(RpnPlan pl, RpnWork ws, co
     const RpnLevel lv = pl.lv[l];
     const int K = lv.K, words = (K + 63) >> 6;
     const unsigned long long* mat = ws.mat + (long long)n * pl.mat_total + lv.mat_first;
-    unsigned long long val = lane < words ? ws.valid[((int64_t)n * pl.L + l) * 64 + lane] : 0ull;
-    if (lane == words - 1 && (K & 63)) val &= (1ull << (K & 63)) - 1ull;
-    unsigned long long rem = 0ull;                                   // word `lane` of the removed set
-    int kept = 0;
-    for (int w = 0; w < words; ++w) {                               // wave-uniform throughout; 64 ranks at a time
-        const unsigned long long vw = rpn_lane_value(val, w);
-        unsigned long long cur = vw & ~rpn_lane_value(rem, w);
-        if (!cur) continue;
-        // the diagonal tile in registers: lane b holds word w of row 64 w + b, the ranks of this block that rank 64 w + b removes
-        const int ib = w * 64 + lane;
-        const unsigned long long diag = ib < K ? mat[(long long)ib * words + w] : 0ull;
-        unsigned long long keep = 0ull;
-        while (cur) {                                               // the greedy walk inside the block: no memory on the chain
-            const int b = __ffsll((long long)cur) - 1;
-            keep |= 1ull << b;
-            cur &= ~(rpn_lane_value(diag, b) | (1ull << b));        // a row holds only bits above its own rank
-        }
-        if ((keep >> lane) & 1ull) kept_rank[kept + __popcll(keep & ((1ull << lane) - 1ull))] = ib;
-        kept += __popcll(keep);
-        if (lane > w && lane < words) {                             // the kept rows into the words after this block, loads in flight together
-            unsigned long long m = keep;
-            while (m) {
-                unsigned long long r[4];
-                int b = 0;
-#pragma unroll
-                for (int q = 0; q < 4; ++q) {                       // four rows per trip; the last row again when fewer are left
-                    b = m ? __ffsll((long long)m) - 1 : b;
-                    m &= m - 1ull;
-                    r[q] = mat[(long long)(w * 64 + b) * words + lane];
-                }
-                rem |= (r[0] | r[1]) | (r[2] | r[3]);
-            }
-        }
-    }
+    unsigned long long val[1] = {ws.valid[((int64_t)n * pl.L + l) * 64 + lane] & nms_all_valid(lane, K)};
+    const int kept = nms_greedy_scan<1>(mat, words, words, K, val, INT_MAX, kept_rank);
     __syncthreads();
-    const int n_valid = wave_sum(__popcll(val));
+    const int n_valid = wave_sum(__popcll(val[0]));
     const int64_t cb = (int64_t)n * pl.cand_total + lv.cand_first;
     for (int j = lane; j < kept; j += 64) {
         const int r = kept_rank[j];
