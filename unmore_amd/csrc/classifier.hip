@@ -40,7 +40,8 @@ __global__ void im2col_nchw_kernel(const float* __restrict__ img, T* __restrict_
         for (int k = C * KH * KW; k < ldk; ++k) out[row * ldk + k] = out_cvt<T>(0.f);
 }
 
-// NHWC, 4 channels per thread
+// NHWC, 4 channels per thread.  A tap replaces the running maximum when `v > m || isnan(v)`, as in umr_maxpool3x3s2_bwd and torch: a NaN
+// in a window reaches its output (fmaxf would drop it)
 template <typename T>
 __global__ void maxpool3x3s2_kernel(const T* __restrict__ x, T* __restrict__ y, int B, int H, int W, int C, int Ho, int Wo) {
     const int c4 = C / 4;
@@ -59,7 +60,8 @@ __global__ void maxpool3x3s2_kernel(const T* __restrict__ x, T* __restrict__ y, 
                 const int ix = ox * 2 - 1 + kx;
                 if ((unsigned)ix >= (unsigned)W) continue;
                 const f32x4 v = Vec4<T>::load(x + (((int64_t)b * H + iy) * W + ix) * C + c);
-                for (int e = 0; e < 4; ++e) m[e] = fmaxf(m[e], v[e]);
+                for (int e = 0; e < 4; ++e)
+                    if (v[e] > m[e] || __builtin_isnan(v[e])) m[e] = v[e];
             }
         }
         Vec4<T>::store(y + (((int64_t)b * Ho + oy) * Wo + ox) * C + c, m);
