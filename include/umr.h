@@ -965,6 +965,27 @@ int umr_det_resize_nearest(const int64_t* desc, int B, const int32_t* tab, int64
 int umr_det_normalize_pad(const int64_t* desc, int B, int Hp, int Wp, float mean0, float mean1, float mean2, float std0, float std1,
                           float std2, float pad_value, float* out, umr_stream_t stream);
 
+/* ---- the tail of the detector's mask head (cad/modeling/roi_heads/roi_heads.py:1098-1201, CustomMaskRCNNConvUpsampleHead: the 1x1
+ * predictor on the ReLU'd 2x2 stride-2 deconvolution; csrc/mask_head.hip) ------------------------------------------------------------------
+ * D [M, 4C] (UMR_F32 / UMR_BF16, contiguous, 16-byte aligned) is the deconvolution GEMM's output after bias and ReLU, as umr_gemm_nt
+ *   stores it: M = R * S * S, row m = (r * S + y) * S + x, column n = (2 * ky + kx) * C + co.  The [R,2S,2S,C] map is never laid out.
+ *   wp: float32 [C], bp: float32 [1], both on the device.
+ * mask_head_logits: logits [R,1,2S,2S] (the type of D, or float32 with out_f32) = bp + sum_co D[m,(ky,kx,co)] * wp[co] at (r, 2y + ky,
+ *   2x + kx), summed in float32 in an order that depends on C and the type alone; sigmoid != 0 stores 1 / (1 + exp(-logit)) instead
+ *   (mask_rcnn_inference).
+ * mask_head_tail_bwd: dlogits [R,1,2S,2S] (the type of D, or float32 with dlogits_f32).  D is OVERWRITTEN with
+ *   G[m,(ky,kx,co)] = D > 0 ? dlogit * wp[co] : 0, the float32 product rounded once to the type of D; dwp float32 [C] = sum over m and
+ *   the taps of dlogit * D[m,(tap,co)], dbp float32 [1] = sum of dlogits.  phases: 1 = G and one float32 partial sum per channel and
+ *   workgroup of 256 rows, 2 = the partials added in a fixed order; 3 = both.  workspace >= mask_head_workspace(M, C) bytes (-1 for
+ *   arguments the launch would refuse), 4-byte aligned.
+ * C a multiple of 64, at most 1024, and 1 <= S <= 64 (else UMR_ERR_UNSUPPORTED); R * S * S < 2^31.  R == 0 is a no-op (tail_bwd with
+ *   phase 2 then stores zeros).  No float atomics, no synchronisation, nothing allocated; the same input gives the same bytes on every run. */
+int64_t umr_mask_head_workspace(int64_t M, int C);
+int umr_mask_head_logits(const void* D, const float* wp, const float* bp, void* logits, int64_t R, int S, int C, int dtype,
+                         int out_f32, int sigmoid, umr_stream_t stream);
+int umr_mask_head_tail_bwd(void* D, const void* dlogits, int dlogits_f32, const float* wp, float* dwp, float* dbp, void* workspace,
+                           int64_t workspace_bytes, int64_t R, int S, int C, int dtype, int phases, umr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
