@@ -986,6 +986,30 @@ int umr_mask_head_logits(const void* D, const float* wp, const float* bp, void* 
 int umr_mask_head_tail_bwd(void* D, const void* dlogits, int dlogits_f32, const float* wp, float* dwp, float* dbp, void* workspace,
                            int64_t workspace_bytes, int64_t R, int S, int C, int dtype, int phases, umr_stream_t stream);
 
+/* ---- the predictors of the RPN head (Detectron2's StandardRPNHead: the 1x1 objectness_logits and anchor_deltas convolutions on the
+ * ReLU'd 3x3 convolution, the same weights on every level; csrc/rpn_head.hip) ------------------------------------------------------------
+ * T [M, C] (UMR_F32 / UMR_BF16, contiguous, 16-byte aligned) is the hidden map of ALL levels stacked, NHWC: level l starts at row
+ *   first_l = sum over the earlier levels of N * H * W, its row (n * H_l + y) * W_l + x.  levels: 4 int64 per level ON THE HOST:
+ *   H, W, and the device pointers of the level's two contiguous NCHW maps [N, A, H, W] and [N, 4A, H, W].  wo float32 [A, C],
+ *   bo float32 [A], wd float32 [4A, C], bd float32 [4A], on the device; the products read them rounded to the compute type.
+ * rpn_head_predict: logits[l][n, a, y, x] = bo[a] + sum_c T[m, c] wo[a, c], deltas[l][n, j, y, x] = bd[j] + sum_c T[m, c] wd[j, c],
+ *   float32 sums on the matrix cores, stored in the type of T or as float32 (out_f32).  T is only read.  One launch for all levels.
+ * rpn_head_predict_bwd: the maps are the incoming gradients dlogits / ddeltas, in the type of T or float32 (grads_f32).  T is
+ *   OVERWRITTEN with G[m, c] = T[m, c] > 0 ? sum_{j < 5A} g[m, j] w[j, c] : 0 rounded once to the type of T; dwo / dbo / dwd / dbd
+ *   float32 in the shapes of wo / bo / wd / bd: sum_m g[m, j] T[m, c] and sum_m g[m, j].  With UMR_BF16 the gradients are rounded to
+ *   bfloat16 before the products (also float32 ones); the bias sums take them as they are.  phases: 1 = G and one float32 partial
+ *   [16][C + 1] per workgroup, 2 = the partials added in a fixed order; 3 = both.  The grid is min(ceil(M / 128), 512) workgroups, a
+ *   function of M alone.  workspace >= rpn_head_workspace(M, C, A) bytes (-1 for shapes the launch would refuse), 4-byte aligned.
+ * 1 <= A <= 3 (5A <= 16), C a multiple of 64 up to 1024, 1 <= n_levels <= 8 (else UMR_ERR_UNSUPPORTED); M < 2^31.  M == 0 is a no-op
+ *   (predict_bwd with phase 2 then stores zeros).  No float atomics, no synchronisation, nothing allocated: the same input gives the
+ *   same bytes on every run and every device. */
+int64_t umr_rpn_head_workspace(int64_t M, int C, int A);
+int umr_rpn_head_predict(const void* T, const int64_t* levels, int n_levels, int64_t N, int C, int A, const float* wo, const float* bo,
+                         const float* wd, const float* bd, int dtype, int out_f32, umr_stream_t stream);
+int umr_rpn_head_predict_bwd(void* T, const int64_t* levels, int n_levels, int64_t N, int C, int A, int grads_f32, const float* wo,
+                             const float* wd, float* dwo, float* dbo, float* dwd, float* dbd, void* workspace, int64_t workspace_bytes,
+                             int dtype, int phases, umr_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif
