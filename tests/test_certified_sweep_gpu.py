@@ -165,3 +165,39 @@ def test_all_1225_proposals_of_one_image_against_the_cpu_oracle():
     print(f"1225 proposals vs the CPU oracle: {n_cert} certified by the oracle ({n_peak_cert} of them with a peak), 0 mismatches among them; "
           f"{len(mism_unc)} uncertified near-ties differ {mism_unc[:10]}; sweep {info}; field error of the first batch {worst_field:.2e}")
     assert n_cert >= 1000 and n_peak_cert >= 20
+
+
+def test_certified_sweep_decides_like_the_full_sweep_at_a_threshold_beside_a_maximum():
+    """The certificate proves `max` stays on its side of the threshold it is GIVEN.  Put the caller's threshold half a certificate bound
+    above the full-precision maximum of a proposal that the default threshold certifies: the sweep must re-run that proposal (its
+    three-term maximum is within sqrt(2) * 1e-4 of the full one, so within the bound of the threshold) and every decision
+    `max > thres` must be the full-precision one -- at that threshold and at the default."""
+    from unmore_amd import ops, reasoning
+    net, _ = _sweep_net()
+    props = _anchors()
+    assert props.shape[0] == 1225
+    image = torch.from_numpy(synth.blob_images(1, 480, 640, seed=1000)[0]).cuda()
+    assert ops.get_f32_mode() == "x3"
+    mx_f, am_f, _ = reasoning.sweep_proposals(net, image, props, 50, precision="full")
+    info0 = {}
+    mx_0, am_0, _ = reasoning.sweep_proposals(net, image, props, 50, precision="certified", info=info0)
+    torch.cuda.synchronize()
+    assert info0["rerun_indices"] == sorted(info0["rerun_indices"]) and len(info0["rerun_indices"]) == info0["rerun"]
+    assert torch.equal(mx_0 > 0.009, mx_f > 0.009)                                   # decisions at the default threshold
+    assert torch.equal(am_0, am_f)
+    mx_full = mx_f.cpu().numpy()
+    rerun0 = set(info0["rerun_indices"])
+    cand = [i for i in range(1225) if mx_full[i] > 0 and i not in rerun0]
+    assert cand, "vacuous: no proposal with a positive peak is certified at the default threshold"
+    cand.sort(key=lambda i: (mx_full[i], i))
+    k = cand[len(cand) // 2]                                                          # the median full-precision maximum
+    bound = 2 * 2 ** 0.5 * reasoning.CERT_EPS
+    thres = float(mx_full[k] + 0.5 * bound)
+    info = {}
+    mx_c, am_c, _ = reasoning.sweep_proposals(net, image, props, 50, precision="certified", info=info, singular_threshold=thres)
+    torch.cuda.synchronize()
+    print(f"certified sweep beside a maximum: proposal {k}, full max {mx_full[k]:.6f}, thres {thres:.6f}; default {info0['rerun']} re-run, "
+          f"here {info['rerun']}; decisions differ at {int(((mx_c > thres) != (mx_f > thres)).sum())} of 1225")
+    assert k in info["rerun_indices"], (k, info["rerun"])
+    assert torch.equal(mx_c > thres, mx_f > thres)
+    assert torch.equal(am_c, am_f)

@@ -193,7 +193,8 @@ class Object_Discovery:
             # unmore_amd's own net: the batches of 50 go round three HIP streams, and in fp32 the sweep is certificate-driven -- three-term
             # products first, six-term only for the proposals whose peak index / side of the threshold is not PROVABLY the six-term one
             # (reasoning.sweep_proposals: 1.7x on a 1 225-proposal image, same indices and decisions; bench.py --workload cfg5)
-            mx, am, _ = reasoning.sweep_proposals(self.objectness_model, image, proposals, precision="certified")
+            mx, am, _ = reasoning.sweep_proposals(self.objectness_model, image, proposals, precision="certified",
+                                                  singular_threshold=float(a.center_score_max_thres))
             H = W = 128
             sdf_maps = center_fields = None
         else:

@@ -167,7 +167,7 @@ _sweep_streams = {}
 CERT_EPS = 2e-4     # the field perturbation the certificate covers: twice the 1e-4 parity contract (tests/golden/make_golden_r2.py: CERT_EPS)
 
 
-def _sweep_pass(objectness_model, image, props, num_img_per_batch, streams, cur, certify):
+def _sweep_pass(objectness_model, image, props, num_img_per_batch, streams, cur, certify, singular_threshold=0.009):
     outs = []
     for s in streams:
         s.wait_stream(cur)
@@ -179,7 +179,7 @@ def _sweep_pass(objectness_model, image, props, num_img_per_batch, streams, cur,
                 pred = objectness_model.get_prediction(crops)
             sdf = pred["sdf_maps"].squeeze(1)
             if certify:
-                mx, am, ce = center_peaks_certified(sdf, pred["center_fields"], CERT_EPS)
+                mx, am, ce = center_peaks_certified(sdf, pred["center_fields"], CERT_EPS, singular_threshold)
             else:
                 mx, am = center_peaks(sdf, pred["center_fields"])
                 ce = torch.ones_like(am, dtype=torch.bool)
@@ -194,7 +194,8 @@ def _sweep_pass(objectness_model, image, props, num_img_per_batch, streams, cur,
     return tuple(torch.cat([o[k] for o in outs]) for k in range(4))
 
 
-def sweep_proposals(objectness_model, image, proposals, num_img_per_batch=50, n_streams=3, precision="full", info=None):
+def sweep_proposals(objectness_model, image, proposals, num_img_per_batch=50, n_streams=3, precision="full", info=None,
+                    singular_threshold=0.009):
     """The per-proposal part of `center_reasoning` + the first half of `optimize_one_image_single_round` for ALL proposals of an
     image (object_reasoning.py:301-337,528-550,139-174): crop + resize, ObjectnessNet maps, centre peaks, boundary box deltas,
     in the reference's batches of 50.  Batches are independent, so consecutive batches are enqueued on `n_streams` HIP streams
@@ -207,7 +208,9 @@ def sweep_proposals(objectness_model, image, proposals, num_img_per_batch=50, n_
                   index is provably the one ANY fields within CERT_EPS = 2e-4 of these maps would give (center_peaks_certified); pass 2
                   re-runs only the proposals without that certificate in the full mode and takes their results from there.  Costs one
                   host synchronisation per image (the reference synchronises per proposal, object_reasoning.py:546-550).
-    info: an optional dict that receives {'proposals', 'rerun', 'certified_in_pass1'}.
+    singular_threshold: the caller's `center_score_max_thres` (object_reasoning.py:541).  The certificate also proves that a proposal's
+      maximum stays on its side of THIS value, so `max > singular_threshold` is the full-precision decision for every proposal.
+    info: an optional dict that receives {'proposals', 'rerun', 'certified_in_pass1', 'rerun_indices'} (the sorted re-run proposal indices).
     Returns (max_values [N] f64, flat_argmax [N] i64, deltas [N,4] f32) on the device."""
     from . import ops
     _need_gpu(image)
@@ -224,16 +227,18 @@ def sweep_proposals(objectness_model, image, proposals, num_img_per_batch=50, n_
     if not certified_mode:
         mx, am, d, _ = _sweep_pass(objectness_model, image, props, num_img_per_batch, streams, cur, certify=False)
         if info is not None:
-            info.update(proposals=len(props), rerun=0, certified_in_pass1=None)
+            info.update(proposals=len(props), rerun=0, certified_in_pass1=None, rerun_indices=[])
         return mx, am, d
     prev = ops.set_f32_mode("x3_fast")
     try:
-        mx, am, d, ce = _sweep_pass(objectness_model, image, props, num_img_per_batch, streams, cur, certify=True)
+        mx, am, d, ce = _sweep_pass(objectness_model, image, props, num_img_per_batch, streams, cur, certify=True,
+                                    singular_threshold=singular_threshold)
     finally:
         ops.set_f32_mode(prev)
     redo = torch.nonzero(~ce).flatten().cpu()          # the one host synchronisation of the image
     if info is not None:
-        info.update(proposals=len(props), rerun=int(redo.numel()), certified_in_pass1=int(len(props) - redo.numel()))
+        info.update(proposals=len(props), rerun=int(redo.numel()), certified_in_pass1=int(len(props) - redo.numel()),
+                    rerun_indices=redo.tolist())
     if redo.numel():
         mx2, am2, d2, _ = _sweep_pass(objectness_model, image, props[redo], num_img_per_batch, streams, cur, certify=False)
         idx = redo.to(dev)
