@@ -218,3 +218,15 @@ def test_pack_cache_param_groups_and_capture_purge():
     assert cache.purge_capture(store) == 1 and ("x", "lin_t", torch.float32) not in cache._o
     assert cache.generation({"hit_o": True}) != (gen[0], gen[1])
     assert cache.purge_capture(store) == 0
+
+
+def test_pack_table_has_the_engine_kinds_and_the_named_builders():
+    """packs.BUILDERS, the one kind -> builder table of Engine._w, Engine._wx3 and the conv heads: exactly the six kinds Engine._w has
+    always accepted, each entry the `_pack_*` function of that layout itself, under the name engine.py re-exports too."""
+    from unmore_amd import engine, packs
+    names = {"lin": "_pack_linear", "lin_t": "_pack_linear_t", "c3": "_pack_conv3", "c3_d": "_pack_conv3_dgrad", "ct": "_pack_convT",
+             "ct_d": "_pack_convT_dgrad"}
+    assert set(packs.BUILDERS) == set(names)
+    for kind, name in names.items():
+        assert packs.BUILDERS[kind] is getattr(packs, name) and getattr(engine, name) is getattr(packs, name), kind
+    assert engine.BUILDERS is packs.BUILDERS

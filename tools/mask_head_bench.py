@@ -26,24 +26,10 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import torch  # noqa: E402
 
+from head_bench_common import module_times, timed  # noqa: E402
+
 C, S = 256, 14
 HBM_BYTES_PER_S = 8e12
-
-
-def timed(fn, windows, iters, warmup=2):
-    """median over the windows of the mean device time of fn() in ms"""
-    for _ in range(warmup):
-        fn()
-    out = []
-    for _ in range(windows):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(iters):
-            fn()
-        b.record()
-        b.synchronize()
-        out.append(a.elapsed_time(b) / iters)
-    return statistics.median(out)
 
 
 def main():
@@ -73,24 +59,8 @@ def main():
     dl = mc.make_dlogits(R, S, args.seed + 2).to(dev).to(dtype)
 
     # ---- the module: every launch, the two halves
-    per_launch, fwd_ms, bwd_ms = {}, [], []
-    for w in range(2 + args.windows):
-        marks = []
-        logits = head.layers(x, _marks=marks)
-        logits.backward(dl)
-        torch.cuda.synchronize()
-        if w < 2:
-            continue
-        names = [n for n, _ in marks]
-        for (n0, e0), (n1, e1) in zip(marks[:-1], marks[1:]):
-            if n1 not in ("fwd_start", "bwd_start"):
-                per_launch.setdefault(n1, []).append(e0.elapsed_time(e1))
-        ev = dict(marks)
-        fwd_ms.append(ev["fwd_start"].elapsed_time(ev["tail_logits"]))
-        bwd_ms.append(ev["bwd_start"].elapsed_time(marks[-1][1]))
-        print(f"window {w - 2}: forward {fwd_ms[-1]:.3f} ms, backward {bwd_ms[-1]:.3f} ms", flush=True)
-    launches_ms = {n: round(statistics.median(v), 4) for n, v in per_launch.items()}
-    forward_ms, backward_ms = statistics.median(fwd_ms), statistics.median(bwd_ms)
+    launches_ms, forward_ms, backward_ms, names = module_times(lambda marks: head.layers(x, _marks=marks).backward(dl), args.windows,
+                                                               "tail_logits")
     trunk_fwd_flop = R * S * S * (4 * C * 9 * C * 2 + 4 * C * C * 2)
     trunk_fwd_ms = sum(launches_ms[n] for n in names if n.startswith("mask_fcn") and "grad" not in n) + launches_ms["deconv"]
     trunk_bwd_ms = sum(v for n, v in launches_ms.items() if n.endswith("grad"))

@@ -18,6 +18,7 @@ windows between device events.
 import argparse
 import json
 import os
+import functools
 import statistics
 import sys
 
@@ -27,31 +28,13 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 import torch  # noqa: E402
 
+import head_bench_common  # noqa: E402
+
+timed = functools.partial(head_bench_common.timed, per_call=True)
+
 C, A = 256, 3
 STRIDES = (4, 8, 16, 32, 64)
 HBM_BYTES_PER_S = 8e12
-
-
-def timed(fn, windows, iters, warmup=2, before=None):
-    """median over the windows of the mean device time of fn() in ms; before(): run ahead of every call, outside the timed span"""
-    for _ in range(warmup):
-        if before:
-            before()
-        fn()
-    out = []
-    for _ in range(windows):
-        tot = 0.0
-        for _ in range(iters):
-            if before:
-                before()
-            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            a.record()
-            fn()
-            b.record()
-            b.synchronize()
-            tot += a.elapsed_time(b)
-        out.append(tot / iters)
-    return statistics.median(out)
 
 
 def main():
@@ -107,25 +90,10 @@ def main():
     print(f"M = {M} rows, {nonzero_rows:.5f} of them with a non-zero real gradient", flush=True)
 
     # ---- the module: every launch, the two halves
-    per_launch, fwd_ms, bwd_ms, names = {}, [], [], []
-    for w in range(2 + args.windows):
-        marks = []
+    def step(marks):
         a, b = head(feats, _marks=marks)
         torch.autograd.backward(a + b, real[0] + real[1])
-        torch.cuda.synchronize()
-        del a, b
-        if w < 2:
-            continue
-        names = [n for n, _ in marks]
-        for (n0, e0), (n1, e1) in zip(marks[:-1], marks[1:]):
-            if n1 not in ("fwd_start", "bwd_start"):
-                per_launch.setdefault(n1, []).append(e0.elapsed_time(e1))
-        ev = dict(marks)
-        fwd_ms.append(ev["fwd_start"].elapsed_time(ev["predict"]))
-        bwd_ms.append(ev["bwd_start"].elapsed_time(marks[-1][1]))
-        print(f"window {w - 2}: forward {fwd_ms[-1]:.3f} ms, backward {bwd_ms[-1]:.3f} ms", flush=True)
-    launches_ms = {n: round(statistics.median(v), 4) for n, v in per_launch.items()}
-    forward_ms, backward_ms = statistics.median(fwd_ms), statistics.median(bwd_ms)
+    launches_ms, forward_ms, backward_ms, _ = head_bench_common.module_times(step, args.windows, "predict")
     trunk_flop = M * C * 9 * C * 2
     trunk_fwd_ms = sum(v for n, v in launches_ms.items() if n.startswith("conv_l"))
     trunk_bwd_ms = sum(v for n, v in launches_ms.items() if n.startswith("conv_wgrad") or n.startswith("conv_dgrad"))

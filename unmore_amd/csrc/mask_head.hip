@@ -17,9 +17,8 @@
 //                      once; a row's four values reach the other lanes as wave-uniform registers.  Every lane adds dlogit * D to
 //                      the sums of its own chunks over the wave's rows; the four waves' sums meet in LDS, wave after wave, then
 //                      the four taps of a channel, in tap order: one f32 partial per channel and workgroup, the workgroup's sum of dlogits after them.
-//   mh_finish_kernel   adds the partials of a channel: wave w of 16 takes the workgroups w, w + 16, ... in index order, the waves' sums are added in
-//                      wave order.  No float atomics anywhere: the same input gives the same bytes on every run.
-#include "umr_common.h"
+//   finish_partials.h  adds the workgroups' partials in a fixed order.  No float atomics anywhere: the same input gives the same bytes on every run.
+#include "finish_partials.h"
 #include <algorithm>
 
 namespace {
@@ -28,21 +27,6 @@ constexpr int MH_THREADS = 256;
 constexpr int MH_ROWS = 256;               // rows of D per workgroup of the backward kernel: 64 per wave
 constexpr int MH_MAX_C = 1024;
 constexpr int MH_MAX_S = 64;
-constexpr int MH_FIN_THREADS = 1024;
-
-template <typename T> struct Chunk;         // 16 bytes of a row
-template <> struct Chunk<float> {
-    static constexpr int V = 4;
-    typedef f32x4 raw;
-    static __device__ __forceinline__ float get(const raw& r, int i) { return r[i]; }
-    static __device__ __forceinline__ void set(raw& r, int i, float v) { r[i] = v; }
-};
-template <> struct Chunk<bf16_t> {
-    static constexpr int V = 8;
-    typedef bf16x8 raw;
-    static __device__ __forceinline__ float get(const raw& r, int i) { return (float)r[i]; }
-    static __device__ __forceinline__ void set(raw& r, int i, float v) { r[i] = (bf16_t)v; }
-};
 
 __device__ __forceinline__ float mh_uniform(float v, int lane) {        // lane `lane` (wave-uniform) of v, as a wave-uniform value
     return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), lane));
@@ -65,7 +49,7 @@ template <typename T, int NP>
 __global__ __launch_bounds__(MH_THREADS) void mh_logits_kernel(const T* __restrict__ D, const float* __restrict__ wp,
                                                                const float* __restrict__ bp, void* __restrict__ out, int64_t M, int S,
                                                                int C, int out_f32, int sigmoid) {
-    typedef Chunk<T> CH;
+    typedef Chunk16<T> CH;
     constexpr int V = CH::V;
     const int lane = threadIdx.x & 63;
     const int row_elems = 4 * C;
@@ -120,7 +104,7 @@ template <typename T, int NP>
 __global__ __launch_bounds__(MH_THREADS) void mh_tail_bwd_kernel(T* __restrict__ D, const void* __restrict__ dlogits, int dl_f32,
                                                                  const float* __restrict__ wp, float* __restrict__ partials, int64_t M,
                                                                  int S, int C) {
-    typedef Chunk<T> CH;
+    typedef Chunk16<T> CH;
     constexpr int V = CH::V;
     extern __shared__ __attribute__((aligned(16))) float mh_sums[];      // [4 * C] the workgroup's sums per column of D, then [4] dlogit sums
     const int tid = threadIdx.x, lane = tid & 63, wv = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -204,27 +188,15 @@ __global__ __launch_bounds__(MH_THREADS) void mh_tail_bwd_kernel(T* __restrict__
     if (tid == 0) part[C] = ((mh_sums[row_elems] + mh_sums[row_elems + 1]) + mh_sums[row_elems + 2]) + mh_sums[row_elems + 3];
 }
 
-// out[c] = sum over the workgroups' partials [n][C + 1]: columns blockIdx.x * 64 .. + 63; column C is dbp
-__global__ __launch_bounds__(MH_FIN_THREADS) void mh_finish_kernel(const float* __restrict__ partials, int64_t n, int C,
-                                                                   float* __restrict__ dwp, float* __restrict__ dbp) {
-    __shared__ float red[MH_FIN_THREADS];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int c = blockIdx.x * 64 + lane;
-    float s = 0.f;
-    if (c <= C)
-        for (int64_t i = wv; i < n; i += MH_FIN_THREADS / 64) s += partials[i * (C + 1) + c];
-    red[tid] = s;
-    __syncthreads();
-    if (wv == 0 && c <= C) {
-        float t = red[lane];
-        for (int k = 1; k < MH_FIN_THREADS / 64; ++k) t += red[k * 64 + lane];
-        if (c < C) dwp[c] = t; else dbp[0] = t;
-    }
-}
+struct MhStore {                            // element c of a record [C + 1]: dwp[c], then dbp
+    float *dwp, *dbp;
+    int C;
+    __device__ void operator()(int c, float v) const { if (c < C) dwp[c] = v; else dbp[0] = v; }
+};
 
 inline int64_t mh_blocks(int64_t M) { return (M + MH_ROWS - 1) / MH_ROWS; }
 
-template <typename T> int mh_passes(int C) { return (4 * C / Chunk<T>::V + 63) / 64; }
+template <typename T> int mh_passes(int C) { return (4 * C / Chunk16<T>::V + 63) / 64; }
 
 int mh_check(int64_t R, int S, int C, int dtype) {
     UMR_CHECK_ARG(dtype == UMR_F32 || dtype == UMR_BF16, "mask_head: the compute type must be UMR_F32 or UMR_BF16");
@@ -256,7 +228,7 @@ void mh_bwd_launch(void* D, const void* dlogits, int dl_f32, const float* wp, fl
         if (np_ <= 1) fn<T, 1>(__VA_ARGS__);                                                 \
         else if (np_ <= 2) fn<T, 2>(__VA_ARGS__);                                            \
         else if (np_ <= 4) fn<T, 4>(__VA_ARGS__);                                            \
-        else fn<T, 4 * MH_MAX_C / Chunk<T>::V / 64>(__VA_ARGS__);                            \
+        else fn<T, 4 * MH_MAX_C / Chunk16<T>::V / 64>(__VA_ARGS__);                          \
     } while (0)
 
 }  // namespace
@@ -300,7 +272,8 @@ extern "C" int umr_mask_head_tail_bwd(void* D, const void* dlogits, int dlogits_
         UMR_LAUNCH_CHECK();
     }
     if (phases & 2) {
-        mh_finish_kernel<<<(C + 1 + 63) / 64, MH_FIN_THREADS, 0, s>>>(partials, R > 0 ? mh_blocks(M) : 0, C, dwp, dbp);
+        finish_partials_kernel<<<(C + 1 + 63) / 64, FINISH_THREADS, 0, s>>>(partials, R > 0 ? mh_blocks(M) : 0, C + 1, C + 1,
+                                                                            MhStore{dwp, dbp, C});
         UMR_LAUNCH_CHECK();
     }
     return UMR_OK;

@@ -23,15 +23,14 @@
 //                       weight-gradient tile stays in registers over all of the wave's rows, up to 256 channels at a time (more channels:
 //                       the rows are walked once per group); all of a pair's loads are issued before its first store; the four waves' sums meet in LDS in wave order: one partial [16][C + 1]
 //                       per workgroup (column C: db).
-//   rh_finish_kernel    adds the partials: wave w of 16 takes the workgroups w, w + 16, ... in index order, the waves' sums are added
-//                       in wave order.
+//   finish_partials.h   adds the partials in a fixed order.
 // The grid of the backward is min(ceil(M / 128), 512) workgroups, a function of M alone; no float atomics: the same input gives the
 // same bytes on every run and every device.
 //
 // Rounding.  The weights are rounded to the compute type before the products (bf16 compute: bf16 weights).  With bf16 compute the
 // incoming gradients g are ROUNDED TO bfloat16 to feed the matrix cores, in G and in dW alike, also when they arrive as float32; db sums
 // them unrounded.  With f32 compute nothing is rounded: the f32 matrix-core products are exact f32 fma chains.
-#include "umr_common.h"
+#include "finish_partials.h"
 #include <algorithm>
 
 namespace {
@@ -41,7 +40,6 @@ constexpr int RH_MAX_C = 1024;
 constexpr int RH_MAX_A = 3;
 constexpr int RH_MAX_LEVELS = 8;
 constexpr int RH_MAX_WG = 512;              // workgroups of the backward, whatever the device
-constexpr int RH_FIN_THREADS = 1024;
 constexpr int RH_MINW = 2;                 // waves per SIMD the backward is compiled for: two hide each other's load latency (measured: 0.50 ms against 0.56 with one)
 
 struct RhTable {                            // by value in the kernel arguments, copied to LDS: lanes index it by their own level
@@ -53,10 +51,6 @@ struct RhTable {                            // by value in the kernel arguments,
 };
 
 struct RhLoc { int lvl, n, yx, hw; };
-
-template <typename T> struct RH;
-template <> struct RH<bf16_t> { static constexpr int V = 8; typedef bf16x8 raw; };
-template <> struct RH<float> { static constexpr int V = 4; typedef f32x4 raw; };
 
 __device__ __forceinline__ f32x4 rh_mma(f32x4 acc, bf16x8 a, bf16x8 b) {
     return __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b, acc, 0, 0, 0);
@@ -109,8 +103,8 @@ template <typename T>
 __global__ __launch_bounds__(RH_THREADS) void rh_predict_kernel(const T* __restrict__ Tm, RhTable tab, int64_t M, int C, int A,
                                                                 const float* __restrict__ wo, const float* __restrict__ bo,
                                                                 const float* __restrict__ wd, const float* __restrict__ bd, int out_f32) {
-    constexpr int V = RH<T>::V, K = 4 * V;
-    typedef typename RH<T>::raw raw;
+    constexpr int V = Chunk16<T>::V, K = 4 * V;
+    typedef typename Chunk16<T>::raw raw;
     extern __shared__ __attribute__((aligned(16))) char rh_smem[];
     T* Wl = (T*)rh_smem;
     const int ldw = C + V;
@@ -171,8 +165,8 @@ template <typename T, int GC>
 __global__ __launch_bounds__(RH_THREADS, RH_MINW) void rh_bwd_kernel(T* __restrict__ Tm, RhTable tab, int64_t M, int C, int A, int g_f32,
                                                             const float* __restrict__ wo, const float* __restrict__ wd,
                                                             float* __restrict__ partials) {
-    constexpr int V = RH<T>::V, K = 4 * V, STEPS = GC / K, NB = GC / 16, H = sizeof(T) == 2 ? 2 : 1;
-    typedef typename RH<T>::raw raw;
+    constexpr int V = Chunk16<T>::V, K = 4 * V, STEPS = GC / K, NB = GC / 16, H = sizeof(T) == 2 ? 2 : 1;
+    typedef typename Chunk16<T>::raw raw;
     extern __shared__ __attribute__((aligned(16))) char rh_smem[];
     T* WT = (T*)rh_smem;
     float* sums = (float*)(rh_smem + (size_t)GC * 16 * sizeof(T));
@@ -338,26 +332,15 @@ __global__ __launch_bounds__(RH_THREADS, RH_MINW) void rh_bwd_kernel(T* __restri
     }
 }
 
-// element e of [5A][C + 1] = sum over the workgroups' partials [n][16][C + 1]; elements blockIdx.x * 64 .. + 63
-__global__ __launch_bounds__(RH_FIN_THREADS) void rh_finish_kernel(const float* __restrict__ partials, int n, int C, int A,
-                                                                   float* __restrict__ dwo, float* __restrict__ dbo,
-                                                                   float* __restrict__ dwd, float* __restrict__ dbd) {
-    __shared__ float red[RH_FIN_THREADS];
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const int e = blockIdx.x * 64 + lane, total = 5 * A * (C + 1);
-    float s = 0.f;
-    if (e < total)
-        for (int i = wv; i < n; i += RH_FIN_THREADS / 64) s += partials[(int64_t)i * 16 * (C + 1) + e];
-    red[tid] = s;
-    __syncthreads();
-    if (wv == 0 && e < total) {
-        float t = red[lane];
-        for (int k = 1; k < RH_FIN_THREADS / 64; ++k) t += red[k * 64 + lane];
+struct RhStore {                            // element e of the first 5A rows of a record [16][C + 1]: row j < A of dwo | dbo, else of dwd | dbd
+    float *dwo, *dbo, *dwd, *dbd;
+    int C, A;
+    __device__ void operator()(int e, float v) const {
         const int j = e / (C + 1), c = e - j * (C + 1);
-        if (j < A) { if (c < C) dwo[j * C + c] = t; else dbo[j] = t; }
-        else { if (c < C) dwd[(j - A) * C + c] = t; else dbd[j - A] = t; }
+        if (j < A) { if (c < C) dwo[j * C + c] = v; else dbo[j] = v; }
+        else { if (c < C) dwd[(j - A) * C + c] = v; else dbd[j - A] = v; }
     }
-}
+};
 
 inline int rh_grid(int64_t M) { return (int)std::min<int64_t>(std::max<int64_t>((M + 127) / 128, 1), RH_MAX_WG); }
 
@@ -392,8 +375,8 @@ int rh_table(const int64_t* levels, int n_levels, int64_t N, int C, int A, int d
 template <typename T>
 void rh_predict_launch(const void* Tm, const RhTable& tab, int64_t M, int C, int A, const float* wo, const float* bo, const float* wd,
                        const float* bd, int out_f32, hipStream_t s) {
-    const int lds = 16 * (C + RH<T>::V) * (int)sizeof(T) + (int)sizeof(RhTable);
-    UMR_SET_MAX_LDS_ONCE((rh_predict_kernel<T>), 16 * (RH_MAX_C + RH<T>::V) * (int)sizeof(T) + (int)sizeof(RhTable));
+    const int lds = 16 * (C + Chunk16<T>::V) * (int)sizeof(T) + (int)sizeof(RhTable);
+    UMR_SET_MAX_LDS_ONCE((rh_predict_kernel<T>), 16 * (RH_MAX_C + Chunk16<T>::V) * (int)sizeof(T) + (int)sizeof(RhTable));
     const int64_t tiles = (M + 15) / 16;
     const int blocks = (int)std::min<int64_t>((tiles + 3) / 4, 4096);
     rh_predict_kernel<T><<<blocks, RH_THREADS, lds, s>>>((const T*)Tm, tab, M, C, A, wo, bo, wd, bd, out_f32);
@@ -459,7 +442,8 @@ extern "C" int umr_rpn_head_predict_bwd(void* T, const int64_t* levels, int n_le
         UMR_LAUNCH_CHECK();
     }
     if (phases & 2) {
-        rh_finish_kernel<<<(5 * A * (C + 1) + 63) / 64, RH_FIN_THREADS, 0, s>>>(partials, M > 0 ? rh_grid(M) : 0, C, A, dwo, dbo, dwd, dbd);
+        finish_partials_kernel<<<(5 * A * (C + 1) + 63) / 64, FINISH_THREADS, 0, s>>>(partials, M > 0 ? rh_grid(M) : 0, 16 * (C + 1),
+                                                                                      5 * A * (C + 1), RhStore{dwo, dbo, dwd, dbd, C, A});
         UMR_LAUNCH_CHECK();
     }
     return UMR_OK;

@@ -47,6 +47,21 @@ template <> struct Vec4<bf16_t> {
     }
 };
 
+// 16 bytes of a row <-> one register vector: V elements (8 bf16 / 4 f32), read and written as float
+template <typename T> struct Chunk16;
+template <> struct Chunk16<float> {
+    static constexpr int V = 4;
+    typedef f32x4 raw;
+    static __device__ __forceinline__ float get(const raw& r, int i) { return r[i]; }
+    static __device__ __forceinline__ void set(raw& r, int i, float v) { r[i] = v; }
+};
+template <> struct Chunk16<bf16_t> {
+    static constexpr int V = 8;
+    typedef bf16x8 raw;
+    static __device__ __forceinline__ float get(const raw& r, int i) { return (float)r[i]; }
+    static __device__ __forceinline__ void set(raw& r, int i, float v) { r[i] = (bf16_t)v; }
+};
+
 __device__ __forceinline__ float gelu_erf(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752440f)); }
 __device__ __forceinline__ float dgelu_erf(float x) {
     const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752440f));

@@ -21,7 +21,7 @@ from . import _lib as L
 from . import graphs
 from . import ops
 from .engine_x3 import X3Numerics, _drop_f, _f
-from .packs import (ParamGroup, PackCache, _ACT, _pack_conv3, _pack_conv3_dgrad, _pack_convT, _pack_convT_dgrad, _pack_linear,
+from .packs import (BUILDERS, ParamGroup, PackCache, _ACT, _pack_conv3, _pack_conv3_dgrad, _pack_convT, _pack_convT_dgrad, _pack_linear,
                     _pack_linear_t, _rep_bias, _unpack_conv3_grad)
 
 CONFIGS = {
@@ -350,15 +350,7 @@ class Engine:
         p = P[name]
         if kind == "lin" and self.dt == torch.float32 and p.dtype == torch.float32 and p.is_contiguous():
             return p.detach().reshape(p.shape[0], -1)    # fp32 mode: the [N, K] kernel layout IS the parameter's layout -- no copy
-
-        return self.cache.get((name, kind, self.dt), p, lambda: {
-            "lin": lambda: _pack_linear(p, self.dt),
-            "lin_t": lambda: _pack_linear_t(p.detach().reshape(p.shape[0], -1), self.dt),
-            "c3": lambda: _pack_conv3(p, self.dt),
-            "c3_d": lambda: _pack_conv3_dgrad(p, self.dt),
-            "ct": lambda: _pack_convT(p, self.dt),
-            "ct_d": lambda: _pack_convT_dgrad(p, self.dt),
-        }[kind]())
+        return self.cache.get((name, kind, self.dt), p, lambda: BUILDERS[kind](p, self.dt))
 
     def _wx3(self, P, name, kind):
         """f32 weights as three bf16 planes per value ([rows, 3K]; conv: K = (ky,kx,ci) inside each plane) for ops.gemm_nt_x3.
@@ -371,8 +363,6 @@ class Engine:
             w = p.detach()
             if kind == "lin":
                 return w.reshape(w.shape[0], -1).contiguous()
-            if kind == "lin_t":
-                return _pack_linear_t(w.reshape(w.shape[0], -1), torch.float32)
             if kind in ("lin_a", "lin_b", "lin_t_a", "lin_t_b"):
                 D = w.shape[1] // 2
                 half = w[:, :D] if kind.endswith("a") else w[:, D:]
@@ -380,7 +370,7 @@ class Engine:
                     return _pack_linear_t(half, torch.float32)
                 out = torch.empty((w.shape[0], D), dtype=torch.float32, device=w.device)
                 return ops.permute4(w, out, (1, 1, w.shape[0], D), (0, 0, w.stride(0), 1), src_offset=(0 if kind.endswith("a") else D))
-            return {"c3": _pack_conv3, "c3_d": _pack_conv3_dgrad, "ct": _pack_convT, "ct_d": _pack_convT_dgrad}[kind](w, torch.float32)
+            return BUILDERS[kind](w, torch.float32)
 
         def build():
             return ops.split3(pack_f32())

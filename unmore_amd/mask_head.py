@@ -10,18 +10,15 @@ out.  Activations are stored in the compute type as the GEMMs round them and the
 backward see the same ReLU masks.  No CPU fallback: tests/mask_head_common.py restates the head in float64 from torch's own ops."""
 import torch
 
+from . import _conv_head as H
 from . import _lib as L
 from . import _tables as T
 from . import mask_loss, ops, packs, roi_sample
 from .ops import _p, _stream
 
-MAX_CHANNELS = 1024
+MAX_CHANNELS = H.MAX_CHANNELS
 MAX_SIDE = 64
-_DTYPES = (torch.float32, torch.bfloat16)
-
-
-def _device(tensors, what):
-    return T.one_device(tensors, "mask_head", what)
+_DTYPES = H.DTYPES
 
 
 def _check_tail(D, wp, bp, R, S, what):
@@ -49,7 +46,7 @@ def tail_logits(D, wp, bp, R, S, *, out_f32=False, sigmoid=False):
     column (2*ky + kx)*C + co; wp float32 [C], bp float32 [1].  Returns [R,1,2S,2S] in D's type (float32 with out_f32):
     bp + sum_co D*wp at (2y + ky, 2x + kx), float32 sums; sigmoid=True stores the probability instead."""
     C = _check_tail(D, wp, bp, R, S, "tail_logits")
-    dev = _device([D, wp, bp], "tail_logits")
+    dev = T.one_device([D, wp, bp], "mask_head", "tail_logits")
     with torch.cuda.device(dev):
         out = torch.empty((R, 1, 2 * S, 2 * S), dtype=torch.float32 if out_f32 else D.dtype, device=dev)
         L.check(L.lib().umr_mask_head_logits(_p(D), _p(wp), _p(bp), _p(out), R, S, C, T.dtype_code(D), int(bool(out_f32)), int(bool(sigmoid)),
@@ -67,7 +64,7 @@ def tail_bwd(D, dlogits, wp, R, S, *, _phase_ms=None):
             or not dlogits.is_contiguous():
         raise ValueError(f"mask_head: tail_bwd: dlogits must be contiguous [{R}, 1, {2 * S}, {2 * S}] in D's type or float32, got "
                          f"{getattr(dlogits, 'dtype', type(dlogits))} {list(getattr(dlogits, 'shape', []))}")
-    dev = _device([D, dlogits, wp], "tail_bwd")
+    dev = T.one_device([D, dlogits, wp], "mask_head", "tail_bwd")
     with torch.cuda.device(dev):
         dwp, dbp = torch.empty(C, dtype=torch.float32, device=dev), torch.empty(1, dtype=torch.float32, device=dev)
         nbytes = L.lib().umr_mask_head_workspace(R * S * S, C)
@@ -78,14 +75,6 @@ def tail_bwd(D, dlogits, wp, R, S, *, _phase_ms=None):
                                                    nbytes, R, S, C, T.dtype_code(D), phases, _stream()), "umr_mask_head_tail_bwd")
         T.timed(launch, (("tail_bwd", 1), ("tail_finish", 2)), _phase_ms)
     return D, dwp, dbp
-
-
-def _mark(marks, name):
-    """tools/mask_head_bench.py times every launch: with a list, a device event after the launch called `name`"""
-    if marks is not None:
-        ev = torch.cuda.Event(enable_timing=True)
-        ev.record()
-        marks.append((name, ev))
 
 
 def _unpack_convT_grad(dwp, grad_out):  # [(i,j,co)][ci] f32 -> ConvTranspose2d's [ci,co,2,2] f32
@@ -109,23 +98,23 @@ class _Layers(torch.autograd.Function):
         with torch.cuda.device(dev):
             cin = int(x.shape[1])
             a = torch.empty((R, S, S, cin), dtype=dt, device=dev)
-            _mark(marks, "fwd_start")
-            ops.permute4(x.detach(), a, (R, S, S, cin), (cin * S * S, S, 1, S * S))            # NCHW -> NHWC, cast to the compute type
-            _mark(marks, "to_nhwc")
+            H.mark(marks, "fwd_start")
+            H.permutes([H.to_nhwc(x.detach(), a)])                                               # cast to the compute type
+            H.mark(marks, "to_nhwc")
             acts = [a]
             for k in range(nconv):
                 w, b = params[2 * k], params[2 * k + 1]
                 a = ops.gemm_nt(a, head._pack(f"mask_fcn{k + 1}.weight", "c3", w, dt), b.detach(), conv=1, act=L.ACT_RELU)
                 a = a.view(R, S, S, -1)
                 acts.append(a)
-                _mark(marks, f"mask_fcn{k + 1}")
+                H.mark(marks, f"mask_fcn{k + 1}")
             wd, bd, wpred, bpred = params[2 * nconv:2 * nconv + 4]
-            brep = head._pack("deconv.bias", "rep", bd, torch.float32)
+            brep = head._cache.get(("deconv.bias", "rep", torch.float32), bd, lambda: packs._rep_bias(bd, 4))
             D = ops.gemm_nt(a.view(R * S * S, -1), head._pack("deconv.weight", "ct", wd, dt), brep, act=L.ACT_RELU)
-            _mark(marks, "deconv")
+            H.mark(marks, "deconv")
             wp = wpred.detach().view(-1)
             logits = tail_logits(D, wp, bpred.detach(), R, S, sigmoid=sigmoid)
-            _mark(marks, "tail_logits")
+            H.mark(marks, "tail_logits")
         ctx.save_for_backward(*acts, D, *params)
         if keep is not None:
             keep["acts"], keep["D"] = acts, D.clone()          # the backward writes G over D
@@ -138,12 +127,9 @@ class _Layers(torch.autograd.Function):
         nconv = head.num_conv
         need = ctx.needs_input_grad                              # (x, cfg, *params)
         if R == 0:
-            params = ctx.saved_tensors
             gx = torch.zeros((0, head.in_channels, S, S), dtype=ctx.x_dtype, device=dlogits.device) if need[0] else None
-            return (gx, None) + tuple(torch.zeros_like(p) if need[2 + i] else None for i, p in enumerate(params))
-        if ctx.done:
-            raise RuntimeError("mask_head: the backward writes its gradient over the stored deconvolution output: it runs once per forward")
-        ctx.done = True
+            return (gx, None) + H.zeros_like_needed(ctx.saved_tensors, need[2:])
+        H.once(ctx, "mask_head", "deconvolution output")
         saved = ctx.saved_tensors
         acts, D, params = saved[:nconv + 1], saved[nconv + 1], saved[nconv + 2:]
         wd, bd, wpred, bpred = params[2 * nconv:2 * nconv + 4]
@@ -155,9 +141,9 @@ class _Layers(torch.autograd.Function):
             dl = dlogits.contiguous()
             if dl.dtype not in (dt, torch.float32):
                 dl = dl.float()
-            _mark(marks, "bwd_start")
+            H.mark(marks, "bwd_start")
             G, dwp, dbp = tail_bwd(D, dl, wpred.detach().view(-1), R, S)
-            _mark(marks, "tail_bwd")
+            H.mark(marks, "tail_bwd")
             grads[2 * nconv + 2], grads[2 * nconv + 3] = dwp.view(wpred.shape), dbp.view(bpred.shape)
             a4 = acts[nconv].view(M, -1)
             c4, c5 = int(wd.shape[0]), int(wd.shape[1])
@@ -166,21 +152,18 @@ class _Layers(torch.autograd.Function):
                 dwt = ops.gemm_tn(G, a4, dbias=dbrep)                                            # [(ky,kx,co)][ci]
                 grads[2 * nconv] = _unpack_convT_grad(dwt, torch.empty_like(wd))
                 grads[2 * nconv + 1] = ops.segsum(dbrep, 1, 4, c5, 0, c5).view(bd.shape)        # the four taps in tap order
-                _mark(marks, "deconv_wgrad")
+                H.mark(marks, "deconv_wgrad")
             # the input of the deconvolution went through a ReLU unless it is x itself
             da = ops.gemm_nt(G, head._pack("deconv.weight", "ct_d", wd, dt), aux=(a4 if nconv else None), mask_relu=nconv > 0)
-            _mark(marks, "deconv_dgrad")
+            H.mark(marks, "deconv_dgrad")
             if kept is not None:
                 kept["G"], kept[f"da{nconv}"] = G, da
             for k in range(nconv, 0, -1):
                 w, b = params[2 * (k - 1)], params[2 * (k - 1) + 1]
                 below = acts[k - 1]
                 if need[2 + 2 * (k - 1)] or need[2 + 2 * (k - 1) + 1]:
-                    db = torch.empty(b.shape, dtype=torch.float32, device=dev)
-                    dwk = ops.gemm_tn(da.view(M, -1), below, dbias=db, conv=1)                  # [co][ky][kx][ci]
-                    grads[2 * (k - 1)] = packs._unpack_conv3_grad(dwk, torch.empty_like(w))
-                    grads[2 * (k - 1) + 1] = db
-                    _mark(marks, f"mask_fcn{k}_wgrad")
+                    grads[2 * (k - 1)], grads[2 * (k - 1) + 1], _ = H.conv3_param_grads([(da.view(M, -1), below)], w, b)
+                    H.mark(marks, f"mask_fcn{k}_wgrad")
                 if k > 1:
                     da = ops.gemm_nt(da.view(R, S, S, -1), head._pack(f"mask_fcn{k}.weight", "c3_d", w, dt), conv=1, aux=below,
                                      mask_relu=True)
@@ -188,34 +171,21 @@ class _Layers(torch.autograd.Function):
                     da = ops.gemm_nt(da.view(R, S, S, -1), head._pack(f"mask_fcn{k}.weight", "c3_d", w, dt), conv=1)
                 else:
                     da = None
-                _mark(marks, f"mask_fcn{k}_dgrad")
+                H.mark(marks, f"mask_fcn{k}_dgrad")
                 if kept is not None:
                     kept[f"da{k - 1}"] = da
             gx = None
             if need[0]:
-                cin = head.in_channels
-                gx = torch.empty((R, cin, S, S), dtype=ctx.x_dtype, device=dev)
-                ops.permute4(da, gx, (R, cin, S, S), (S * S * cin, 1, S * cin, cin))           # NHWC -> NCHW, in x's type
-                _mark(marks, "to_nchw")
+                gx = torch.empty((R, head.in_channels, S, S), dtype=ctx.x_dtype, device=dev)
+                H.permutes([H.to_nchw(da, gx)])                                                  # in x's type
+                H.mark(marks, "to_nchw")
         if keep is not None:
             keep["grads"] = kept
-        for i in range(len(params)):
-            if not need[2 + i]:
-                grads[i] = None
-        return (gx, None) + tuple(grads)
+        return (gx, None) + H.masked(grads, need[2:])
 
 
-class _Layer(torch.nn.Module):
-    """the parameters of one layer under the reference's names: `weight`, `bias`"""
-
-    def __init__(self, weight_shape, init):
-        super().__init__()
-        self.weight = torch.nn.Parameter(torch.empty(weight_shape, dtype=torch.float32))
-        self.bias = torch.nn.Parameter(torch.zeros(weight_shape[1] if init == "deconv" else weight_shape[0], dtype=torch.float32))
-        if init == "predictor":
-            torch.nn.init.normal_(self.weight, std=0.001)
-        else:                                                    # c2_msra_fill
-            torch.nn.init.kaiming_normal_(self.weight, mode="fan_out", nonlinearity="relu")
+def _msra_fill(w):                                               # c2_msra_fill
+    torch.nn.init.kaiming_normal_(w, mode="fan_out", nonlinearity="relu")
 
 
 class MaskRCNNConvUpsampleHead(torch.nn.Module):
@@ -248,18 +218,16 @@ class MaskRCNNConvUpsampleHead(torch.nn.Module):
         if len(conv_dims) < 1:
             raise ValueError("mask_head: conv_dims have to be non-empty")
         for c in (in_channels,) + conv_dims:
-            if not isinstance(c, int) or isinstance(c, bool) or c < 64 or c % 64 or c > MAX_CHANNELS:
-                raise ValueError(f"mask_head: every channel count must be a multiple of 64 up to {MAX_CHANNELS}, got {c!r}")
-        if compute_dtype not in (None,) + _DTYPES:
-            raise ValueError(f"mask_head: compute_dtype must be None, float32 or bfloat16, got {compute_dtype!r}")
+            H.check_channels(c, "mask_head: every channel count")
+        H.check_compute_dtype(compute_dtype, "mask_head")
         self.in_channels, self.conv_dims, self.num_conv = in_channels, conv_dims, len(conv_dims) - 1
         self.use_soft_targets, self.loss_weight, self.vis_period, self.compute_dtype = bool(use_soft_targets), loss_weight, vis_period, compute_dtype
         cur = in_channels
         for k, c in enumerate(conv_dims[:-1]):
-            self.add_module(f"mask_fcn{k + 1}", _Layer((c, cur, 3, 3), "conv"))
+            self.add_module(f"mask_fcn{k + 1}", H.Layer((c, cur, 3, 3), _msra_fill))
             cur = c
-        self.deconv = _Layer((cur, conv_dims[-1], 2, 2), "deconv")
-        self.predictor = _Layer((1, conv_dims[-1], 1, 1), "predictor")
+        self.deconv = H.Layer((cur, conv_dims[-1], 2, 2), _msra_fill, bias_dim=1)
+        self.predictor = H.Layer((1, conv_dims[-1], 1, 1), lambda w: torch.nn.init.normal_(w, std=0.001))
         self._cache = packs.PackCache()
 
     def _params(self):
@@ -270,10 +238,7 @@ class MaskRCNNConvUpsampleHead(torch.nn.Module):
         return ps + [self.deconv.weight, self.deconv.bias, self.predictor.weight, self.predictor.bias]
 
     def _pack(self, name, kind, p, dt):
-        build = {"c3": lambda: packs._pack_conv3(p, dt), "c3_d": lambda: packs._pack_conv3_dgrad(p, dt),
-                 "ct": lambda: packs._pack_convT(p, dt), "ct_d": lambda: packs._pack_convT_dgrad(p, dt),
-                 "rep": lambda: packs._rep_bias(p, 4)}[kind]
-        return self._cache.get((name, kind, dt), p, build)
+        return self._cache.get((name, kind, dt), p, lambda: packs.BUILDERS[kind](p, dt))
 
     def layers(self, x, *, _keep=None, _sigmoid=False, _marks=None):
         if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.dtype not in _DTYPES or x.shape[1] != self.in_channels \
@@ -283,10 +248,8 @@ class MaskRCNNConvUpsampleHead(torch.nn.Module):
         if x.shape[0] * x.shape[2] * x.shape[3] >= 1 << 31:
             raise ValueError("mask_head: R*S*S must be below 2^31")
         params = self._params()
-        for p in params:
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise ValueError("mask_head: the parameters are contiguous float32 master copies")
-        _device([x] + params, "MaskRCNNConvUpsampleHead.layers")
+        H.check_master_copies(params, "mask_head")
+        T.one_device([x] + params, "mask_head", "MaskRCNNConvUpsampleHead.layers")
         if not x.is_contiguous():
             x = x.contiguous()
         dt = self.compute_dtype or x.dtype

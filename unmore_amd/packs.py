@@ -265,7 +265,8 @@ def _pack_linear(w, dt):  # [N,K] -> [N,K] T
     return ops.cast(w.detach().reshape(w.shape[0], -1), dt)
 
 
-def _pack_linear_t(w2d, dt):  # [N,K] (possibly strided rows) -> [K,N] T
+def _pack_linear_t(w, dt):  # [N,K] (possibly strided rows) or [N,...] contiguous -> [K,N] T
+    w2d = w.detach().reshape(w.shape[0], -1)
     N, K = w2d.shape
     out = torch.empty((K, N), dtype=dt, device=w2d.device)
     return ops.permute4(w2d, out, (1, 1, K, N), (0, 0, w2d.stride(1), w2d.stride(0)), src_offset=0)
@@ -307,3 +308,8 @@ def _pack_convT_dgrad(w, dt):  # -> [ci][(i,j,co)]
 def _rep_bias(b, reps):
     out = torch.empty(reps * b.numel(), dtype=torch.float32, device=b.device)
     return ops.permute4(b.detach(), out, (1, 1, reps, b.numel()), (0, 0, 0, 1))
+
+
+# kind -> builder(parameter, compute type) of the layouts Engine._w, Engine._wx3 and the conv heads ask for by name
+BUILDERS = {"lin": _pack_linear, "lin_t": _pack_linear_t, "c3": _pack_conv3, "c3_d": _pack_conv3_dgrad, "ct": _pack_convT,
+            "ct_d": _pack_convT_dgrad}

@@ -20,24 +20,20 @@ import ctypes
 
 import torch
 
+from . import _conv_head as H
 from . import _lib as L
 from . import _tables as T
 from . import ops, packs, rpn, rpn_loss
 from .ops import _p, _stream
 
-MAX_CHANNELS = 1024
+MAX_CHANNELS = H.MAX_CHANNELS
 MAX_ANCHORS = 3              # 5A <= 16: one matrix-core tile (csrc/rpn_head.hip: RH_MAX_A)
 MAX_LEVELS = rpn.MAX_LEVELS
-_DTYPES = (torch.float32, torch.bfloat16)
-
-
-def _device(tensors, what):
-    return T.one_device(tensors, "rpn_head", what)
+_DTYPES = H.DTYPES
 
 
 def _check_shape(C, A, what):
-    if not isinstance(C, int) or isinstance(C, bool) or C < 64 or C % 64 or C > MAX_CHANNELS:
-        raise ValueError(f"rpn_head: {what}: C must be a multiple of 64 up to {MAX_CHANNELS}, got {C!r}")
+    H.check_channels(C, f"rpn_head: {what}: C")
     if not isinstance(A, int) or isinstance(A, bool) or not 1 <= A <= MAX_ANCHORS:
         raise ValueError(f"rpn_head: {what}: between 1 and {MAX_ANCHORS} anchors per position (5A <= 16), got {A!r}")
 
@@ -94,7 +90,7 @@ def predict(Tm, sizes, N, wo, bo, wd, bd, *, out_f32=False):
     wd [4A, C], bd [4A] float32.  Returns (logits, deltas): lists of [N, A, H_l, W_l] and [N, 4A, H_l, W_l] in Tm's type (float32 with
     out_f32), one launch.  Tm is only read."""
     C, A, M, _ = _check_tail(Tm, sizes, N, (wo, bo, wd, bd), "predict")
-    dev = _device([Tm, wo, bo, wd, bd], "predict")
+    dev = T.one_device([Tm, wo, bo, wd, bd], "rpn_head", "predict")
     odt = torch.float32 if out_f32 else Tm.dtype
     with torch.cuda.device(dev):
         logits = [torch.empty((N, A, int(h), int(w)), dtype=odt, device=dev) for h, w in sizes]
@@ -122,7 +118,7 @@ def predict_bwd(Tm, sizes, N, dlogits, ddeltas, wo, wd, *, _phase_ms=None):
                 or g.dtype != maps[0].dtype:
             raise ValueError(f"rpn_head: predict_bwd: gradient map {k} must be contiguous {list(shape)}, all in T's type or all float32, got "
                              f"{getattr(g, 'dtype', type(g))} {list(getattr(g, 'shape', []))}")
-    dev = _device([Tm, wo, wd] + maps, "predict_bwd")
+    dev = T.one_device([Tm, wo, wd] + maps, "rpn_head", "predict_bwd")
     with torch.cuda.device(dev):
         dwo, dbo = torch.empty((A, C), dtype=torch.float32, device=dev), torch.empty(A, dtype=torch.float32, device=dev)
         dwd, dbd = torch.empty((4 * A, C), dtype=torch.float32, device=dev), torch.empty(4 * A, dtype=torch.float32, device=dev)
@@ -136,23 +132,6 @@ def predict_bwd(Tm, sizes, N, dlogits, ddeltas, wo, wd, *, _phase_ms=None):
                                                      _stream()), "umr_rpn_head_predict_bwd")
         T.timed(launch, (("predict_bwd", 1), ("predict_finish", 2)), _phase_ms)
     return Tm, dwo, dbo, dwd, dbd
-
-
-def _mark(marks, name):
-    """tools/rpn_head_bench.py times every launch: with a list, a device event after the launch called `name`"""
-    if marks is not None:
-        ev = torch.cuda.Event(enable_timing=True)
-        ev.record()
-        marks.append((name, ev))
-
-
-def _permutes(recipes):
-    """the recorded (src, dst, dims, strides) permutes: one batched launch when there are several"""
-    if len(recipes) == 1:
-        src, dst, dims, strides = recipes[0]
-        ops.permute4(src, dst, dims, strides)
-    elif recipes:
-        ops.permute4_batched([r + (0,) for r in recipes])()
 
 
 def _is_nhwc(f, dt):
@@ -185,7 +164,7 @@ class _Head(torch.autograd.Function):
             first.append(M)
             M += N * h * w
         with torch.cuda.device(dev):
-            _mark(marks, "fwd_start")
+            H.mark(marks, "fwd_start")
             # NCHW -> NHWC in the compute type: nothing for a channels_last map that already has it, one launch for the others
             xs, recipes = {}, []
             need = [k for k in live if not _is_nhwc(feats[k], dt)]
@@ -201,17 +180,17 @@ class _Head(torch.autograd.Function):
                     f = f.contiguous()
                 xs[k] = stack[at:at + N * h * w].view(N, h, w, C)
                 at += N * h * w
-                recipes.append((f, xs[k], (N, h, w, C), (C * h * w, w, 1, h * w)))
-            _permutes(recipes)
-            _mark(marks, "to_nhwc")
+                recipes.append(H.to_nhwc(f, xs[k]))
+            H.permutes(recipes)
+            H.mark(marks, "to_nhwc")
             Tm = torch.empty((M, C), dtype=dt, device=dev)
             wpack = head._pack("conv.weight", "c3", cw, dt)
             for i, k in enumerate(live):
                 h, w = sizes[k]
                 ops.gemm_nt(xs[k], wpack, cb.detach(), conv=1, act=L.ACT_RELU, out=Tm[first[i]:first[i] + N * h * w])
-                _mark(marks, f"conv_l{k}")
+                H.mark(marks, f"conv_l{k}")
             lg, dl = predict(Tm, lsizes, N, wo.detach(), bo.detach(), wd.detach(), bd.detach())
-            _mark(marks, "predict")
+            H.mark(marks, "predict")
             for i, k in enumerate(live):
                 logits[k], deltas[k] = lg[i], dl[i]
         ctx.first = first
@@ -228,12 +207,9 @@ class _Head(torch.autograd.Function):
         need = ctx.needs_input_grad                              # (cfg, *features, *params)
         dev = gouts[0].device
         if not live:
-            params = ctx.saved_tensors
             gf = [torch.zeros((N, C, h, w), dtype=ctx.f_dtypes[k], device=dev) if need[1 + k] else None for k, (h, w) in enumerate(sizes)]
-            return (None,) + tuple(gf) + tuple(torch.zeros_like(p) if need[1 + nl + i] else None for i, p in enumerate(params))
-        if ctx.done:
-            raise RuntimeError("rpn_head: the backward writes its gradient over the stored hidden map: it runs once per forward")
-        ctx.done = True
+            return (None,) + tuple(gf) + H.zeros_like_needed(ctx.saved_tensors, need[1 + nl:])
+        H.once(ctx, "rpn_head", "hidden map")
         saved = ctx.saved_tensors
         xs, Tm, params = saved[:len(live)], saved[len(live)], saved[len(live) + 1:]
         cw, cb, wo, bo, wd, bd = params
@@ -248,21 +224,14 @@ class _Head(torch.autograd.Function):
             gmaps = [g.contiguous() if g.dtype == gdt else g.to(gdt).contiguous() for g in gmaps]
             if kept is not None:
                 kept["dlogits"], kept["ddeltas"] = gmaps[:len(live)], gmaps[len(live):]
-            _mark(marks, "bwd_start")
+            H.mark(marks, "bwd_start")
             G, dwo, dbo, dwd, dbd = predict_bwd(Tm, lsizes, N, gmaps[:len(live)], gmaps[len(live):], wo.detach(), wd.detach())
-            _mark(marks, "predict_bwd")
+            H.mark(marks, "predict_bwd")
             grads[2], grads[3], grads[4], grads[5] = dwo.view(wo.shape), dbo, dwd.view(wd.shape), dbd
             if need[1 + nl] or need[1 + nl + 1]:
-                # one packed weight gradient [co][ky][kx][ci] and one bias gradient for all levels: umr_gemm_tn adds to both under `accumulate`
-                dwk = torch.empty((C, 9 * C), dtype=torch.float32, device=dev)
-                db = torch.empty(C, dtype=torch.float32, device=dev)
-                for i, k in enumerate(live):
-                    h, w = sizes[k]
-                    ops.gemm_tn(G[first[i]:first[i] + N * h * w], xs[i], dW=dwk, dbias=db, accumulate=i > 0, conv=1)
-                    _mark(marks, f"conv_wgrad_l{k}")
-                grads[0] = packs._unpack_conv3_grad(dwk, torch.empty_like(cw))
-                grads[1] = db
-                _mark(marks, "conv_wgrad_unpack")
+                rows = [G[first[i]:first[i] + N * sizes[k][0] * sizes[k][1]] for i, k in enumerate(live)]    # one packed buffer for all levels
+                grads[0], grads[1], dwk = H.conv3_param_grads(list(zip(rows, xs)), cw, cb, marks, [f"conv_wgrad_l{k}" for k in live])
+                H.mark(marks, "conv_wgrad_unpack")
                 if kept is not None:
                     kept["dwk"] = dwk
             if any(need[1 + k] for k in live):
@@ -274,12 +243,12 @@ class _Head(torch.autograd.Function):
                         continue
                     h, w = sizes[k]
                     dx = ops.gemm_nt(G[first[i]:first[i] + N * h * w].view(N, h, w, C), wdg, conv=1)
-                    _mark(marks, f"conv_dgrad_l{k}")
+                    H.mark(marks, f"conv_dgrad_l{k}")
                     dxs.append(dx)
                     gfeat[k] = torch.empty((N, C, h, w), dtype=ctx.f_dtypes[k], device=dev)
-                    recipes.append((dx, gfeat[k], (N, C, h, w), (h * w * C, 1, w * C, C)))          # NHWC -> NCHW, in the feature's type
-                _permutes(recipes)
-                _mark(marks, "to_nchw")
+                    recipes.append(H.to_nchw(dx, gfeat[k]))                                        # in the feature's type
+                H.permutes(recipes)
+                H.mark(marks, "to_nchw")
                 if kept is not None:
                     kept["dx"] = dxs
             for k, (h, w) in enumerate(sizes):
@@ -289,20 +258,11 @@ class _Head(torch.autograd.Function):
                 kept["G"] = G
         if keep is not None:
             keep["grads"] = kept
-        for i in range(6):
-            if not need[1 + nl + i]:
-                grads[i] = None
-        return (None,) + tuple(gfeat) + tuple(grads)
+        return (None,) + tuple(gfeat) + H.masked(grads, need[1 + nl:])
 
 
-class _Layer(torch.nn.Module):
-    """the parameters of one convolution under Detectron2's names: `weight`, `bias`; normal(std=0.01) and zeros"""
-
-    def __init__(self, weight_shape):
-        super().__init__()
-        self.weight = torch.nn.Parameter(torch.empty(weight_shape, dtype=torch.float32))
-        self.bias = torch.nn.Parameter(torch.zeros(weight_shape[0], dtype=torch.float32))
-        torch.nn.init.normal_(self.weight, std=0.01)
+def _init(w):
+    torch.nn.init.normal_(w, std=0.01)
 
 
 class StandardRPNHead(torch.nn.Module):
@@ -326,12 +286,11 @@ class StandardRPNHead(torch.nn.Module):
         if box_dim != 4:
             raise ValueError(f"rpn_head: only box dimension 4 is implemented, got box_dim={box_dim!r}")
         _check_shape(in_channels, num_anchors, "StandardRPNHead")
-        if compute_dtype not in (None,) + _DTYPES:
-            raise ValueError(f"rpn_head: compute_dtype must be None, float32 or bfloat16, got {compute_dtype!r}")
+        H.check_compute_dtype(compute_dtype, "rpn_head")
         self.in_channels, self.num_anchors, self.box_dim, self.compute_dtype = in_channels, num_anchors, box_dim, compute_dtype
-        self.conv = _Layer((in_channels, in_channels, 3, 3))
-        self.objectness_logits = _Layer((num_anchors, in_channels, 1, 1))
-        self.anchor_deltas = _Layer((num_anchors * box_dim, in_channels, 1, 1))
+        self.conv = H.Layer((in_channels, in_channels, 3, 3), _init)
+        self.objectness_logits = H.Layer((num_anchors, in_channels, 1, 1), _init)
+        self.anchor_deltas = H.Layer((num_anchors * box_dim, in_channels, 1, 1), _init)
         self._cache = packs.PackCache()
 
     def _params(self):
@@ -339,8 +298,7 @@ class StandardRPNHead(torch.nn.Module):
                 self.anchor_deltas.bias]
 
     def _pack(self, name, kind, p, dt):
-        build = {"c3": lambda: packs._pack_conv3(p, dt), "c3_d": lambda: packs._pack_conv3_dgrad(p, dt)}[kind]
-        return self._cache.get((name, kind, dt), p, build)
+        return self._cache.get((name, kind, dt), p, lambda: packs.BUILDERS[kind](p, dt))
 
     def forward(self, features, *, _keep=None, _marks=None):
         if not isinstance(features, (list, tuple)) or not 1 <= len(features) <= MAX_LEVELS:
@@ -357,10 +315,8 @@ class StandardRPNHead(torch.nn.Module):
         if M >= 1 << 31:
             raise ValueError(f"rpn_head: {M} positions over all levels and images, 2^31 or more")
         params = self._params()
-        for p in params:
-            if p.dtype != torch.float32 or not p.is_contiguous():
-                raise ValueError("rpn_head: the parameters are contiguous float32 master copies")
-        _device(list(features) + params, "StandardRPNHead.forward")
+        H.check_master_copies(params, "rpn_head")
+        T.one_device(list(features) + params, "rpn_head", "StandardRPNHead.forward")
         dt = self.compute_dtype or features[0].dtype
         out = _Head.apply((self, dt, _keep, _marks), *features, *params)
         nl = len(features)
